@@ -16,7 +16,7 @@ one camera and one pose per frame; every input resident in HBM before the timed 
 
 Numerics: the headline is the bit-exact f32 path (colour accumulation on f32 MFMAs, identical to
 the CPU oracle); --split-bf16 measures the tolerance mode instead (the line then carries the f32
-number under `exact_accum`); by default the split-bf16 number is an extra key (`split_bf16`).
+number under `exact_accum`); with --full the split-bf16 number is an extra key (`split_bf16`).
 
 N GPUs: one process per GPU.  `--gpus N` starts the N ranks itself (torch.distributed.run, before
 anything touches the GPU) unless it already runs under a launcher (WORLD_SIZE set, which must
@@ -27,10 +27,17 @@ as GUAVA's 8-bit RGB (to8b, main/test.py:85) and all-gathered over RCCL/xGMI to 
 overlapped with the next step's rendering (the timed region ends after the last exchange).  The
 line's time is the max over ranks.
 
-Prints ONE JSON line (rank 0) with the contract fields plus:
+A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs when
+`--dump-outputs DIR` is given (DIR/<name>.npy, float32, the same inputs on every run) and prints ONE
+JSON line (rank 0) with the contract fields.  `--full` adds every secondary measurement, each a run
+of its own after the timed steps:
   roofline        -- render_fwd kernel: algorithmic bytes per launch / average launch time from HIP
-                     events recorded on the launch stream inside the timed region; `traffic` from the
-                     committed PMC summary only when it was measured on this build (source hash);
+                     events recorded on the launch stream (inside the timed region with one batch in
+                     flight, else an isolated pass); `traffic` from the committed PMC summary only
+                     when it was measured on this build (source hash);
+  split_bf16, one_in_flight, deform_ms_per_step, render_work_per_frame, render_mfma,
+  config4_train, config5_cross -- the other colour-accumulation mode, one batch in flight, deform
+                     alone, the render work counters, BASELINE configs 4 and 5 (N=1);
   cpu_baseline    -- the CPU oracle (a port of the reference algorithm) timed on a bounded sample of
                      the same workload on this host's cores (rank 0, N=1 only);
   per_frame_dropin-- GUAVA's own fps definition (main/test.py:70-76,90): deform + one
@@ -100,6 +107,15 @@ def _args():
     ap.add_argument("--no-extras", action="store_true",
                     help="only the contract measurement (no split-bf16 / per-frame / config-3 extras)")
     ap.add_argument("--stages", action="store_true", help="also time every stage (extra events)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement: the isolated kernel-time "
+                         "pass (roofline), deform alone, the render work counters, the other colour-accumulation "
+                         "mode, one batch in flight, GUAVA's per-frame loop, configs 3/4/5 and the CPU baseline "
+                         "(--no-extras / --no-cpu-baseline / --cpu-seconds trim them); without it the run is "
+                         "set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32; arrays above 2M elements as a fixed, seeded sample)")
     a = ap.parse_args()
     if a.batch is None:
         a.batch = 6 if a.pipeline == "train" else 32
@@ -258,6 +274,7 @@ class Workload:
                     rng = np.random.default_rng(5)  # random-init conv_body_first (nn.Conv2d(32, 16, 1))
                     head = RefineHead(t(rng.uniform(-0.18, 0.18, (16, 32)).astype(np.float32)),
                                       t(rng.uniform(-0.18, 0.18, 16).astype(np.float32)), keep_channels=4)
+                self.refine_head = head
                 pipes = self.pipes
                 # fused: Gaussian assembly inside the projection kernel (gsr_forward_batch_deformed);
                 # no refiner epilogue on that entry, so --refine keeps the two-step path
@@ -489,6 +506,45 @@ def config_line(a, config, pipeline, dev, numerics, steps, warmup=5):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 21  # per array: 8 MiB of float32, at most seven arrays per pipeline (< 64 MB in all)
+
+
+def _step_outputs(a, w, res):
+    """What the caller of the timed path holds after a step, by name (device tensors)."""
+    if a.pipeline == "train":  # the step returns the loss; its effect is the updated attributes
+        return dict({"loss": res}, **{k: v.detach() for k, v in w.trainer.p.items()})
+    if a.pipeline == "frame":
+        return {"color": res[0], "invdepth": res[1], "radii": res[2]}
+    out = {"color": res[0], "invdepth": res[1], "radii": res[2]}
+    if a.pipeline == "avatar":
+        if a.refine:  # the fused refiner epilogue writes its output here (batch.RefineHead.out)
+            out["refine_out"] = w.refine_head.out
+        if res[3] is not None:  # the deformed assets (absent on the fused-assembly entry)
+            out.update({k: res[3][k] for k in ("xyz", "scaling", "rotation")})
+    return out
+
+
+def dump_outputs(path, named, rank=0):
+    """Write each tensor as <path>/<name>.npy in float32 (ranks above 0: <name>.rank<r>.npy).  An
+    array above DUMP_MAX_ELEMS elements is written as a sample of its flattened elements at sorted
+    indices drawn from a generator seeded by the name and the element count alone, so two builds
+    write the same elements."""
+    import zlib
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, ten in named.items():
+        flat = ten.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+            idx = np.sort(rng.integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+            arr = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            arr = ten.detach()
+        arr = arr.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+
+
 def main():
     a = _args()
     ws = os.environ.get("WORLD_SIZE")
@@ -586,9 +642,12 @@ def main():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize(dev)
+        last = None
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        if steps > 0:
+            last = step()  # the last step's result is kept for --dump-outputs
         if gatherer is not None:
             gatherer.wait()
         torch.cuda.synchronize(dev)
@@ -598,7 +657,7 @@ def main():
             tt = torch.tensor([el], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        return el
+        return el, last
 
     gatherer = make_gatherer(B)
     step = make_step(w, gatherer)
@@ -621,10 +680,13 @@ def main():
     # isolated pass afterwards, one batch at a time
     isolated = n_inflight > 1
     profile_enable(() if isolated else stage_set)
-    el = timed(step, gatherer, a.steps, 0)
+    el, last = timed(step, gatherer, a.steps, 0)
     prof = profile_read()
     profile_enable(())
-    if isolated:
+    if a.dump_outputs:  # before anything below reuses the pipelines' output buffers
+        dump_outputs(a.dump_outputs, _step_outputs(a, w, last), rank)
+    del last
+    if isolated and a.full:
         profile_enable(stage_set)
         for _ in range(max(20, a.steps // 4)):
             with torch.cuda.stream(streams[0]):
@@ -637,9 +699,9 @@ def main():
             "capacity overflow inside the timed region"
     else:
         assert not any(r.status()[1] for r in w.rasts), "capacity overflow inside the timed region"
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras
     deform_ms = None
-    if a.pipeline == "avatar":  # deformation alone (EHM + Gaussian assembly), outside the timed region
+    if a.full and a.pipeline == "avatar":  # deformation alone (EHM + Gaussian assembly), outside the timed region
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.steps):
@@ -654,7 +716,7 @@ def main():
         for r in w.rasts:
             r.numerics = other
         n_o = max(20, a.steps // 4)
-        el_o = timed(step, None, n_o, 3)
+        el_o, _ = timed(step, None, n_o, 3)
         for r in w.rasts:
             r.numerics = numerics
         other_line = {"value": round(B * n_o / el_o, 2), "ms_per_step": round(1e3 * el_o / n_o, 4), "steps": n_o,
@@ -664,18 +726,18 @@ def main():
     one_line = None
     if extras and dist is None and n_inflight > 1 and a.pipeline in ("avatar", "raster"):
         n_1 = max(20, a.steps // 4)
-        el_1 = timed(make_step(w, None, inflight=1), None, n_1, 3)
+        el_1, _ = timed(make_step(w, None, inflight=1), None, n_1, 3)
         one_line = {"value": round(B * n_1 / el_1, 2), "ms_per_step": round(1e3 * el_1 / n_1, 4), "steps": n_1,
                     "batches_in_flight": 1}
     # work counters of one extra (instrumented, untimed) step: which wall the render kernel hits
-    work = render_counters(step, device=dev)
+    work = render_counters(step, device=dev) if a.full else None
     # config 3 at N>1: the 32-frame batch split over the ranks (strong scaling) beside the weak line
     strong_line = None
     if extras and dist is not None and scaling == "weak" and a.pipeline == "avatar" and 32 % world == 0:
         w3 = Workload(a, wl, 32 // world, rank * (32 // world), 32, dev, numerics)
         g3 = make_gatherer(32 // world)
         n3 = max(20, a.steps // 4)
-        el3 = timed(make_step(w3, g3), g3, n3, 5)
+        el3, _ = timed(make_step(w3, g3), g3, n3, 5)
         strong_line = {"value": round(32 * n3 / el3, 2), "ms_per_step": round(1e3 * el3 / n3, 4), "steps": n3,
                        "global_batch": 32, "frames_per_gpu": 32 // world, "scaling": "strong"}
         del w3, g3
@@ -759,31 +821,33 @@ def main():
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
                      "traffic": traffic, "traffic_source": traffic_note, "alg_bytes_per_launch": bytes_launch,
-                     "avg_launch_ms": round(render_ms, 4),
-                     "timing": "isolated pass, one batch in flight" if isolated else "timed region"},
+                     "avg_launch_ms": round(render_ms, 4) if rcnt else None,
+                     "timing": "timed region" if not isolated else
+                     "isolated pass, one batch in flight" if a.full else "not measured (isolated pass: --full)"},
         "path_roofline": {"alg_bytes_per_frame": _path_alg_bytes(P, W, H),
                           "achieved_GBs": round(_path_alg_bytes(P, W, H) * fps / 1e9, 1),
                           "frac": round(_path_alg_bytes(P, W, H) * fps / 1e9 / HBM_PEAK_GBS, 4)},
     }
     # per-frame work of the render kernel and its matrix-core utilisation (dense peak of the MFMA used)
-    ksteps = work["mfma_ksteps"]
-    if not split_head:
-        mfma_flops = ksteps * 2 * (2 * 32 * 32 * 2)  # two v_mfma_f32_32x32x2f32 per wave k-step
-    else:  # two v_mfma_f32_32x32x8_bf16 per wave k-step (every k-slot carries a split product)
-        mfma_flops = ksteps * 2 * (2 * 32 * 32 * 8)
-    out["render_work_per_frame"] = {k: round(v / B, 1) for k, v in work.items()}
-    out["render_mfma"] = {"issued_tflops": round(mfma_flops / (render_ms * 1e-3) / 1e12, 2) if render_ms else None,
-                          "peak_tflops": BF16_MFMA_PEAK_TFLOPS if split_head else F32_MFMA_PEAK_TFLOPS,
-                          "instruction": "v_mfma_f32_32x32x8_bf16" if split_head else "v_mfma_f32_32x32x2_f32",
-                          # lane-pairs blended: 64 pixels per survivor in the strip layout
-                          "useful_frac": round(work["pairs_contributing"] / max(64 * work["strip_pairs_blended"], 1),
-                                               4)}
-    if issue is not None:
-        # the compute wall beside the HBM one: per-launch instruction counts and per-SIMD pipe busy
-        # of the contract kernel, from the committed PMC passes of this build
-        out["render_issue"] = dict(issue, source="profiles/pmc_render_fwd.json (tools/gpu_pmc.sh)",
-                                   valu_per_kstep=round(issue["valu_insts"] / max(ksteps, 1), 1)
-                                   if issue.get("valu_insts") else None)
+    if work is not None:
+        ksteps = work["mfma_ksteps"]
+        if not split_head:
+            mfma_flops = ksteps * 2 * (2 * 32 * 32 * 2)  # two v_mfma_f32_32x32x2f32 per wave k-step
+        else:  # two v_mfma_f32_32x32x8_bf16 per wave k-step (every k-slot carries a split product)
+            mfma_flops = ksteps * 2 * (2 * 32 * 32 * 8)
+        out["render_work_per_frame"] = {k: round(v / B, 1) for k, v in work.items()}
+        out["render_mfma"] = {"issued_tflops": round(mfma_flops / (render_ms * 1e-3) / 1e12, 2) if render_ms else None,
+                              "peak_tflops": BF16_MFMA_PEAK_TFLOPS if split_head else F32_MFMA_PEAK_TFLOPS,
+                              "instruction": "v_mfma_f32_32x32x8_bf16" if split_head else "v_mfma_f32_32x32x2_f32",
+                              # lane-pairs blended: 64 pixels per survivor in the strip layout
+                              "useful_frac": round(work["pairs_contributing"] / max(64 * work["strip_pairs_blended"], 1),
+                                                   4)}
+        if issue is not None:
+            # the compute wall beside the HBM one: per-launch instruction counts and per-SIMD pipe busy
+            # of the contract kernel, from the committed PMC passes of this build
+            out["render_issue"] = dict(issue, source="profiles/pmc_render_fwd.json (tools/gpu_pmc.sh)",
+                                       valu_per_kstep=round(issue["valu_insts"] / max(ksteps, 1), 1)
+                                       if issue.get("valu_insts") else None)
     if a.pipeline == "train":
         bms, bcnt = prof.get("render_bwd", (0.0, 0))
         bwd_ms = bms / max(bcnt, 1)
@@ -813,7 +877,7 @@ def main():
         # driver's multi-GPU runs: --pipeline train / --config c5 with --gpus N)
         out["config4_train"] = config_line(a, "c2", "train", dev, numerics, steps=max(a.steps, 100))
         out["config5_cross"] = config_line(a, "c5", "avatar", dev, numerics, steps=max(a.steps, 40))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.pipeline != "train":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.pipeline != "train":
         out["cpu_baseline"] = cpu_baseline(w.scene, w.cams, W, H, a.cpu_seconds, w.avatar_inputs)
     if rank == 0:
         print(json.dumps(out), flush=True)

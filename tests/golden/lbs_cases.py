@@ -90,7 +90,7 @@ def full_cases():
     """SURVEY.md §8(c)'s full-size cases: SMPL-X body lbs_wobeta at V = 10,595, J = 55 (B = 2,
     axis-angle pose, joints_offset) and the FLAME head lbs at FLAME size (V = 5,023, J = 5, 400
     shape + expression betas, B = 2).  The inputs (62 MB of posedirs) are regenerated from the seeds;
-    lbs_golden_full.npz keeps the reference's outputs and the inputs' SHA-256."""
+    lbs_golden_full*.npz keep the reference's outputs and the inputs' SHA-256."""
     cases = {}
     rng = np.random.default_rng(41)
     verts = _teeth_template()
@@ -113,6 +113,20 @@ def full_cases():
                                    parents=m["parents"], lbs_weights=m["lbs_weights"],
                                    joints_offset=None, pose2rot=True)
     return cases
+
+
+FULL_GOLDEN_FILES = ("lbs_golden_full.npz", "lbs_golden_full_T.npz")  # the per-vertex transforms apart
+
+
+def load_full_golden():
+    """The reference's outputs of full_cases() as one dict, read from FULL_GOLDEN_FILES (two files,
+    so that each stays below 1 MiB)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = {}
+    for name in FULL_GOLDEN_FILES:
+        with np.load(os.path.join(here, name)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def digest(case):

@@ -22,7 +22,7 @@ import lbs_cases  # noqa: E402
 
 REF = "/root/reference/models/modules/flame/lbs.py"
 OUT = os.path.join(HERE, "lbs_golden.npz")
-OUT_FULL = os.path.join(HERE, "lbs_golden_full.npz")  # SMPL-X / FLAME full-size cases
+OUT_FULL, OUT_FULL_T = (os.path.join(HERE, f) for f in lbs_cases.FULL_GOLDEN_FILES)  # SMPL-X / FLAME full-size cases
 
 
 def _ref_module():
@@ -64,6 +64,8 @@ def main():
     ref = _ref_module()
     for path, cases in ((OUT, lbs_cases.all_cases()), (OUT_FULL, lbs_cases.full_cases())):
         out = run_cases(ref, cases)
+        if path == OUT_FULL:  # the per-vertex transforms in a file of their own: each stays below 1 MiB
+            np.savez_compressed(OUT_FULL_T, **{k: out.pop(k) for k in list(out) if k.endswith("/T")})
         np.savez_compressed(path, **out)
         print(path, {k: v.shape for k, v in out.items()})
 

@@ -63,13 +63,13 @@ def test_lbs_with_betas_golden_case():
 
 @pytest.fixture(scope="module")
 def full_golden():
-    return np.load(os.path.join(HERE, "golden", "lbs_golden_full.npz")), lbs_cases.full_cases()
+    return lbs_cases.load_full_golden(), lbs_cases.full_cases()
 
 
 @pytest.mark.parametrize("frames", [(0, 1), (1,)])
 def test_full_size_goldens_match_reference(full_golden, frames):
     """The GPU LBS at SURVEY.md §8(c)'s sizes against the reference's own lbs.py outputs
-    (lbs_golden_full.npz): SMPL-X lbs_wobeta at V = 10,595, J = 55 and FLAME lbs at V = 5,023 with
+    (lbs_golden_full*.npz): SMPL-X lbs_wobeta at V = 10,595, J = 55 and FLAME lbs at V = 5,023 with
     400 betas; both frames as one batch, and frame 1 alone (B = 1: the single-frame blend kernel)."""
     from guava_renderer_amd import deform
     gold, cases = full_golden

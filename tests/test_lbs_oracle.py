@@ -135,7 +135,7 @@ def test_deform_identity_pose_keeps_gaussians():
 
 @pytest.fixture(scope="module")
 def full():
-    return np.load(os.path.join(HERE, "golden", "lbs_golden_full.npz")), lbs_cases.full_cases()
+    return lbs_cases.load_full_golden(), lbs_cases.full_cases()
 
 
 def test_full_size_lbs_matches_reference(full):

@@ -16,7 +16,7 @@ for r in 1 2 3; do
   i=0
   for V in "$@"; do
     i=$((i+1))
-    env $(echo "$V" | tr ',' ' ') timeout -k 10 300 python bench.py --pipeline ${PIPE:-avatar} --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --stages > $O/v$i.json 2> $O/v$i.err; rc=$?
+    env $(echo "$V" | tr ',' ' ') timeout -k 10 300 python bench.py --full --pipeline ${PIPE:-avatar} --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --stages > $O/v$i.json 2> $O/v$i.err; rc=$?
     [ $rc -eq 0 ] || { echo "$V rc=$rc"; tail -5 $O/v$i.err; exit $rc; }
     python - "$V" "$O/v$i.json" <<'PY'
 import json, sys

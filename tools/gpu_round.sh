@@ -12,9 +12,9 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log
   [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json
 [ $rc -eq 0 ] || { tail -20 $OUT/bench.err; exit $rc; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 bench.py --inflight 1 --no-cpu-baseline --no-extras --steps 100 --warmup 10 > $OUT/kt.log 2>&1; rc=$?; echo "kt rc=$rc"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --pipeline train --steps 200 --warmup 10 > $OUT/bench_train.json 2> $OUT/bench_train.err; rc=$?; echo "train rc=$rc"; tail -1 $OUT/bench_train.json
+timeout -k 10 300 python bench.py --full --pipeline train --steps 200 --warmup 10 > $OUT/bench_train.json 2> $OUT/bench_train.err; rc=$?; echo "train rc=$rc"; tail -1 $OUT/bench_train.json
 exit $rc

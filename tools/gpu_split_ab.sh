@@ -19,7 +19,7 @@ for r in $(seq 1 ${R:-2}); do
       *) A="--cu-split $V" ;;
     esac
     tag=$(echo "$V" | tr -c 'A-Za-z0-9_\n' '_')
-    timeout -k 10 300 python bench.py --inflight ${INFL:-4} --no-cpu-baseline --no-extras --steps ${STEPS:-100} \
+    timeout -k 10 300 python bench.py --full --inflight ${INFL:-4} --no-cpu-baseline --no-extras --steps ${STEPS:-100} \
       --warmup 10 $A > $O/$tag.json 2> $O/$tag.err
     rc=$?
     [ $rc -eq 0 ] || { echo "$V rc=$rc"; tail -5 $O/$tag.err; exit $rc; }
