@@ -279,7 +279,7 @@ __global__ __launch_bounds__(kScanBlock) void k_bucket_count(Dims d, GeomArena g
     if (!g.tiles[gid]) return;
     const uint32_t kmin = ~g.fstat[kFsWords * b + kFsNotKeyMax], kmax = g.fstat[kFsWords * b + kFsKeyMax];
     const uint32_t bk = bucket_of(__float_as_uint(g.depth[gid]), kmin, bucket_scale(kmin, kmax, d.NB), d.NB);
-    g.bslot[gid] = atomicAdd(&g.bstart[(int64_t)b * (d.NB + 1) + bk], 1u);
+    g.bslot[gid] = atomicAdd(&g.bcount[(int64_t)b * (d.NB + 1) + bk], 1u);
 }
 
 // The same arrival slots with the counting done in LDS: a workgroup takes kCountPer x 1024
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(kCountThreads) void k_bucket_count_lds(Dims d, Geom
         }
     }
     __syncthreads();
-    uint32_t* bs = g.bstart + (int64_t)b * (d.NB + 1);
+    uint32_t* bs = g.bcount + (int64_t)b * (d.NB + 1);
     // the workgroup's claims, all of a thread's returning atomics in flight together (NB <= 16384
     // = 16 per thread here; a loop that waits for each claim before the next costs a frame's
     // latency-bound single launch ~16 memory round trips)
@@ -399,22 +399,26 @@ __global__ __launch_bounds__(kCountThreads) void k_bucket_count_lds(Dims d, Geom
     }
 }
 
-// One workgroup per frame: bucket counts -> bucket starts (entry NB = visible count); buckets
-// longer than kTinyBucket go to the segment-sort worklist.  The table (NB + 1 <= 16385 words) is
-// staged through LDS with coalesced loads and stores; each thread scans a contiguous run of it
-// there (odd run length: conflict-free), so no thread walks global memory at a stride.
+// One workgroup per frame: bucket counts (bcount) -> bucket starts (bstart, entry NB = visible
+// count); buckets longer than kTinyBucket go to the segment-sort worklist.  The counts stay as they
+// are (the fused scatter below keeps the same convention: there other workgroups still read them).
+// The table (NB + 1 <= 16385 words) is staged through LDS with coalesced loads and stores; each
+// thread scans a contiguous run of it there (odd run length: conflict-free), so no thread walks
+// global memory at a stride.
 constexpr int kBucketScanLds = (1 << 14) + 1;
 __global__ __launch_bounds__(1024) void k_bucket_scan(Dims d, GeomArena g) {
     __shared__ uint32_t sh[1024 / 64 + 1];
     __shared__ uint32_t tab[kBucketScanLds];
     if (g.ctrl[kCtrlOverflow]) return;
     const int b = blockIdx.x;
+    const uint32_t* bc = g.bcount + (int64_t)b * (d.NB + 1);
     uint32_t* bs = g.bstart + (int64_t)b * (d.NB + 1);
     const int n = d.NB + 1;
     const bool staged = n <= kBucketScanLds;  // uniform (NB <= 16384 up to 512k Gaussians)
-    uint32_t* t = staged ? tab : bs;
+    const uint32_t* t = staged ? tab : bc;    // counts
+    uint32_t* ts = staged ? tab : bs;         // starts (staged: in place in LDS)
     if (staged) {
-        for (int k = threadIdx.x; k < n; k += 1024) tab[k] = bs[k];
+        for (int k = threadIdx.x; k < n; k += 1024) tab[k] = bc[k];
         __syncthreads();
     }
     const int per = (n + 1023) / 1024;
@@ -426,7 +430,7 @@ __global__ __launch_bounds__(1024) void k_bucket_scan(Dims d, GeomArena g) {
     uint32_t ex = block_excl_scan<uint32_t, 1024>(s, &total, sh);  // (barriers inside)
     for (int k = beg; k < end; k++) {
         const uint32_t c = t[k];
-        t[k] = ex;
+        ts[k] = ex;
         if (c > (uint32_t)kTinyBucket) g.big[atomicAdd(&g.ctrl[kCtrlNumBig], 1u)] = (uint32_t)(b * d.NB + k);
         ex += c;
     }
@@ -438,9 +442,11 @@ __global__ __launch_bounds__(1024) void k_bucket_scan(Dims d, GeomArena g) {
 }
 
 // SCAN (one frame, NB + 1 words fitting the LDS): k_bucket_scan folded in -- every workgroup scans
-// the frame's bucket counts itself in LDS (the same runs and block scan as k_bucket_scan, so the same
-// starts), and workgroup 0 writes the starts back, lists the large buckets and the visible count:
-// one launch fewer per single-frame forward.
+// the frame's bucket counts (bcount) itself in LDS (the same runs and block scan as k_bucket_scan, so
+// the same starts), and workgroup 0 writes the starts to bstart, lists the large buckets and the
+// visible count: one launch fewer per single-frame forward.  Nothing orders the workgroups of the
+// launch, so nothing in it may write bcount: a workgroup that starts after workgroup 0 has finished
+// must still find counts there.
 template <bool SCAN = false>
 __global__ __launch_bounds__(kScanBlock) void k_bucket_scatter(Dims d, GeomArena g) {
     extern __shared__ uint32_t btab[];  // SCAN: the frame's NB + 1 bucket starts
@@ -451,7 +457,8 @@ __global__ __launch_bounds__(kScanBlock) void k_bucket_scatter(Dims d, GeomArena
     if constexpr (SCAN) {
         __shared__ uint32_t sh[kScanBlock / 64 + 1];
         const int n = d.NB + 1;
-        for (int k = threadIdx.x; k < n; k += kScanBlock) btab[k] = bs[k];
+        const uint32_t* bc = g.bcount + (int64_t)b * (d.NB + 1);
+        for (int k = threadIdx.x; k < n; k += kScanBlock) btab[k] = bc[k];
         __syncthreads();
         const int per = (n + kScanBlock - 1) / kScanBlock;
         const int beg = threadIdx.x * per, end = min(n, beg + per);

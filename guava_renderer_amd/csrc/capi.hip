@@ -149,6 +149,7 @@ size_t carve_geom(char* base, const Dims& d, GeomArena* g) {
     a.blocksums = take<uint32_t>(base, off, (size_t)d.B * d.nblk + 1);
     a.blockkey = take<uint32_t>(base, off, (size_t)d.B * d.nblk * 2);
     a.bslot = take<uint32_t>(base, off, n);
+    a.bcount = take<uint32_t>(base, off, (size_t)d.B * (d.NB + 1));
     a.bstart = take<uint32_t>(base, off, (size_t)d.B * (d.NB + 1));
     a.skey = take<uint64_t>(base, off, n);
     a.big = take<uint32_t>(base, off, (size_t)d.B * d.NB);

@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(256) void k_deform_preprocess(int fpw, GsrDeformInp
             __syncthreads();
         }
         // the frame's depth-bucket counters (k_preprocess's duty)
-        for (int k = i; k <= d.NB; k += d.nblk * kScanBlock) g.bstart[(int64_t)b * (d.NB + 1) + k] = 0u;
+        for (int k = i; k <= d.NB; k += d.nblk * kScanBlock) g.bcount[(int64_t)b * (d.NB + 1) + k] = 0u;
         const int64_t gid = (int64_t)b * P + i;
         uint32_t tiles = 0;
         if (i < P) {

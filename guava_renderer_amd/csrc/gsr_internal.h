@@ -95,7 +95,9 @@ struct GeomArena {
     uint32_t* blockkey;   // per scan block: max depth key, max ~depth key of its visible Gaussians
     // per-frame depth sort of the visible Gaussians (bucket sort on the depth float bits)
     uint32_t* bslot;      // per Gaussian: arrival slot inside its depth bucket
-    uint32_t* bstart;     // per frame NB+1 bucket counts, scanned in place to bucket starts
+    uint32_t* bcount;     // per frame NB+1 bucket counts (zeroed by preprocess, claimed by the count
+                          // kernels; never rewritten: every workgroup of the fused scatter scans them)
+    uint32_t* bstart;     // per frame NB+1 bucket starts: the exclusive scan of bcount, entry NB = visible
     uint64_t* skey;       // per frame, (depth bits << 32 | index) grouped by bucket
     uint32_t* big;        // worklist of buckets longer than kTinyBucket: frame * NB + bucket
     uint32_t* order;      // per frame, visible Gaussians in (depth, index) order

@@ -20,25 +20,44 @@ def _carve(spec):
     return out
 
 
+def layout_bytes(layout):
+    """Size of a carved arena (carve_*: the last slab's end, aligned, plus a 256-byte tail)."""
+    return _align(max(off + dt.itemsize * count for off, dt, count in layout.values())) + 256
+
+
+# gsr_internal.h: control words, per-frame words behind them, depth-sort sizes
+CTRL_WORDS, FS_WORDS = 9216, 8
+CTRL_NUM_BIG = 3
+FS_NOT_KEY_MAX, FS_KEY_MAX, FS_VISIBLE = 0, 1, 2
+TINY_BUCKET, SORT_SMALL_CAP, SORT_LARGE_CAP = 64, 2048, 8192
+
+
 def _nb(P):
+    """make_dims: depth buckets per frame, P / 16 up to 2^14 (2^20 above 512k Gaussians)."""
+    cap = (1 << 14) if P <= (1 << 19) else (1 << 20)
     nb = 64
-    while nb < P // 8 and nb < (1 << 20):
+    while nb < P // 16 and nb < cap:
         nb <<= 1
     return nb
 
 
-def geom_layout(P, W, H):
+def geom_layout(P, W, H, B=1):
+    """carve_geom of make_dims(B, P, W, H): per-frame slabs hold B frames back to back."""
     nblk = (P + 255) // 256
     T = ((W + 15) // 16) * ((H + 15) // 16)
     NB = _nb(P)
     chunk = 1024 if T > 1024 else 256  # make_dims: count-table rows
     nchunk = (P + chunk - 1) // chunk
-    return _carve([("ctrl", np.uint32, 9216 + 8), ("depth", np.float32, P), ("invdepth", np.float32, P),
-                   ("radii", np.int32, P), ("means2D", np.float32, 2 * P), ("cov3D", np.float32, 6 * P),
-                   ("conic", np.float32, 4 * P), ("rect", np.uint32, 2 * P), ("rrec", np.float32, 8 * P),
-                   ("tiles", np.uint32, P), ("blocksums", np.uint32, nblk + 1), ("blockkey", np.uint32, 2 * nblk), ("bslot", np.uint32, P),
-                   ("bstart", np.uint32, NB + 1), ("skey", np.uint64, P), ("big", np.uint32, NB),
-                   ("order", np.uint32, P), ("table", np.uint32, nchunk * T)])
+    n = B * P
+    return _carve([("ctrl", np.uint32, CTRL_WORDS + FS_WORDS * B), ("depth", np.float32, n),
+                   ("invdepth", np.float32, n), ("radii", np.int32, n), ("means2D", np.float32, 2 * n),
+                   ("cov3D", np.float32, 6 * n), ("conic", np.float32, 4 * n), ("rect", np.uint32, 2 * n),
+                   ("rrec", np.float32, 8 * n), ("tiles", np.uint32, n), ("blocksums", np.uint32, B * nblk + 1),
+                   ("blockkey", np.uint32, 2 * B * nblk), ("bslot", np.uint32, n),
+                   ("bcount", np.uint32, B * (NB + 1)), ("bstart", np.uint32, B * (NB + 1)),
+                   ("skey", np.uint64, n), ("big", np.uint32, B * NB), ("order", np.uint32, n),
+                   ("table", np.uint32, B * nchunk * T), ("fsplit", np.uint32, P * C),
+                   ("gterm", np.float32, 8 * n)])
 
 
 def image_layout(W, H):
@@ -69,6 +88,51 @@ def make_scene(kind="random", P=2000, W=128, H=96, seed=0, yaw=0.0, pitch=0.0):
         d = scenes.avatar_cloud(P, seed)
     cam = camera.camera(W, H, yaw=yaw, pitch=pitch)
     d.update(cam)
+    d["bg"] = np.zeros(C, np.float32)
+    return d
+
+
+def depth_cloud(P, seed, mode, levels=None, zspread=1.0, outliers=False, culled=0.0, small=1.0):
+    """scenes.random_cloud with its z column rewritten to steer the per-frame depth sort.  With yaw 0
+    the view rotation is the identity, so view depth is fl(z + camera distance): equal z gives equal
+    depth bits.
+      mode "plane":   every z = 0.125 -- one depth bucket holds every visible key, all tied
+           "levels":  z drawn uniformly from `levels` (exact float32 values; repeat a value to weight
+                      it) -- a few big all-tied buckets
+           "squeeze": z * zspread
+      outliers: Gaussian 0 at (0, -0.6, -15) with scale 1e-3 and Gaussian 1 at (0, -0.6, 68), both on
+                the optical axis and in front of the camera for distances 20..25: they stretch the key
+                range so the cloud falls into a few buckets of mostly distinct keys
+      culled:   that fraction moved to x = 5 (off screen): V < P, and the order is not the identity
+                on ties
+      small:    scales multiplied by it (fewer instances, a quicker oracle)"""
+    from guava_renderer_amd import scenes
+    d = scenes.random_cloud(P, seed)
+    rng = np.random.default_rng(seed + 7919)
+    m = d["means3D"]
+    if mode == "plane":
+        m[:, 2] = np.float32(0.125)
+    elif mode == "levels":
+        m[:, 2] = np.asarray(levels, np.float32)[rng.integers(0, len(levels), P)]
+    elif mode == "squeeze":
+        m[:, 2] = (m[:, 2] * np.float32(zspread)).astype(np.float32)
+    else:
+        raise ValueError(mode)
+    d["scales"] = (d["scales"] * np.float32(small)).astype(np.float32)
+    if culled > 0.0:
+        m[rng.random(P) < culled, 0] = np.float32(5.0)
+    if outliers:
+        m[0] = (0.0, -0.6, -15.0)
+        d["scales"][0] = np.float32(1e-3)
+        m[1] = (0.0, -0.6, 68.0)
+    return d
+
+
+def depth_scene(P, seed, mode, W=64, H=64, distance=22.0, **kw):
+    """depth_cloud seen by the canonical camera (yaw 0) at `distance`, as make_scene returns it."""
+    from guava_renderer_amd import camera
+    d = depth_cloud(P, seed, mode, **kw)
+    d.update(camera.camera(W, H, distance=distance))
     d["bg"] = np.zeros(C, np.float32)
     return d
 
@@ -118,7 +182,9 @@ def gpu_forward(d, antialiasing=False, use_cov=None, debug=False, numerics=0):
     P = d["means3D"].shape[0]
     W, H = d["image_width"], d["image_height"]
     st = {}
-    st.update(decode(gb.cpu().numpy(), geom_layout(P, W, H)))
+    gl = geom_layout(P, W, H)
+    assert layout_bytes(gl) == gb.numel(), ("geom_layout is out of step with carve_geom", layout_bytes(gl), gb.numel())
+    st.update(decode(gb.cpu().numpy(), gl))
     st.update(decode(ib.cpu().numpy(), image_layout(W, H)))
     # the binning buffer is carved for its capacity: R after the synchronous read-back, the P x tiles
     # bound on the no-sync path
