@@ -288,8 +288,6 @@ __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(2)
             for (int r = 0; r < 16 + 4; r++) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(0.f, crs, (int)kOOB, 0, 0);
         }
 
-        // strip-centred pixel offsets (exact in f32): the moments use lx = x - cx, ly = y - cy
-        const float cx = (float)sx0 + 3.5f, cy = (float)sy0 + 3.5f;
         const float bg_term = -T_final * bg_dot;  // per pixel, so the background term is one fma per slot
         float T = T_final;
         float accum_dot = 0.f, last_gdot = 0.f, last_alpha = 0.f;
@@ -434,39 +432,43 @@ __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(2)
                 if (ABL == 6) acc[j & 15] = fmaf(w, adl[j], acc[j & 15]);  /* timing ablation */
                 else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w, adl[j], acc, 0, 0, 0);
             }
-            // pixel moments of u for slot l&31 over this lane half's 32 pixels (strip rows 4h..4h+3):
-            // lx = (i % 8) - 3.5, ly = (i / 8) - 3.5 + 4h
-            float S0 = 0.f, Sx = 0.f, Sy = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f, Si = 0.f;
+            // pixel moments of u for slot l&31 over this lane half's 32 pixels (strip rows 4h..4h+3),
+            // about the slot's own centre: dx = mean.x - x, dy = mean.y - y as in the reference's
+            // per-pixel sums (backward.cu:597-627).  Moments about the strip centre, expanded about
+            // the Gaussian's afterwards, cancel: X^2 S0 - 2 X Sx + Sxx loses (X / sigma)^2 of f32's
+            // precision, two decimal digits for a Gaussian of half a pixel at a strip's edge.
+            float S0 = 0.f, Sdx = 0.f, Sdy = 0.f, Sdxx = 0.f, Sdxy = 0.f, Sdyy = 0.f, Si = 0.f;
+            const float Xs = cur.ra.x - (float)sx0, Ys = cur.ra.y - (float)(sy0 + 4 * hi);
+            float dxc[8], dxc2[8];  // the 8 columns' dx and dx^2, set once per batch
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                dxc[c] = Xs - (float)c;
+                dxc2[c] = dxc[c] * dxc[c];
+            }
 #pragma unroll 1
             for (int row = 0; row < 4; row++) {  // one strip row (8 pixels) at a time
-                const float ly = (float)row - 3.5f;
+                const float dy = Ys - (float)row;
                 const float* urow = ul + l32 * kBwdPitch + 32 * hi + 8 * row;
                 const float* wrow = wl + l32 * kBwdPitch + 32 * hi + 8 * row;
                 float r0 = 0.f, rx = 0.f, rxx = 0.f, ri = 0.f;
 #pragma unroll
                 for (int c = 0; c < 8; c++) {
-                    const float lx = (float)c - 3.5f;
                     const float uu = urow[c];
                     r0 += uu;
-                    rx = fmaf(uu, lx, rx);
-                    rxx = fmaf(uu, lx * lx, rxx);
+                    rx = fmaf(uu, dxc[c], rx);
+                    rxx = fmaf(uu, dxc2[c], rxx);
                     if (INVD) ri = fmaf(wrow[c], dli_row[32 * hi + 8 * row + c], ri);
                 }
                 S0 += r0;
-                Sx += rx;
-                Sxx += rxx;
-                Sy = fmaf(r0, ly, Sy);
-                Sxy = fmaf(rx, ly, Sxy);
-                Syy = fmaf(r0, ly * ly, Syy);
+                Sdx += rx;
+                Sdxx += rxx;
+                Sdy = fmaf(r0, dy, Sdy);
+                Sdxy = fmaf(rx, dy, Sdxy);
+                Sdyy = fmaf(r0, dy * dy, Sdyy);
                 Si += ri;
             }
-            if (hi) {  // rows 4..7: ly = ly_i + 4
-                Syy = fmaf(8.f, Sy, fmaf(16.f, S0, Syy));
-                Sxy = fmaf(4.f, Sx, Sxy);
-                Sy = fmaf(4.f, S0, Sy);
-            }
-            S0 = add_halves(S0); Sx = add_halves(Sx); Sy = add_halves(Sy);
-            Sxx = add_halves(Sxx); Sxy = add_halves(Sxy); Syy = add_halves(Syy);
+            S0 = add_halves(S0); Sdx = add_halves(Sdx); Sdy = add_halves(Sdy);
+            Sdxx = add_halves(Sdxx); Sdxy = add_halves(Sdxy); Sdyy = add_halves(Sdyy);
             if (INVD) Si = add_halves(Si);
             wave_lds_order();
             // acc[r] at lane l: channel l&31 of the batch's slot (r&3) + 8(r>>2) + 4(l>>5)
@@ -483,16 +485,10 @@ __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(2)
                     __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc[r], crs, (int)off, 0, 0);
                 }
             }
-            // the other terms of slot l&31, from the pixel moments of u about the Gaussian's centre
-            // (dx = X - lx, dy = Y - ly); lanes 0-31 write the slot's kGtWords row to LDS (the record
-            // tile is free now), then 8 lanes per slot add it to the slot's gterm row
+            // the other terms of slot l&31, from the pixel moments of u about the Gaussian's centre;
+            // lanes 0-31 write the slot's kGtWords row to LDS (the record tile is free now), then 8
+            // lanes per slot add it to the slot's gterm row
             {
-                const float X = cur.ra.x - cx, Y = cur.ra.y - cy;
-                const float Sdx = X * S0 - Sx;
-                const float Sdy = Y * S0 - Sy;
-                const float Sdxx = (X * X) * S0 - 2.f * X * Sx + Sxx;
-                const float Sdxy = (X * Y) * S0 - X * Sy - Y * Sx + Sxy;
-                const float Sdyy = (Y * Y) * S0 - 2.f * Y * Sy + Syy;
                 const float o = cur.ra.z;
                 const float ca = -2.0f * cur.rc.x, cb = -cur.rc.y, cc = -2.0f * cur.rc.z;  // conic a, b, c (exact)
                 float* row = reinterpret_cast<float*>(rl) + 8 * l32;

@@ -137,7 +137,7 @@ def depth_scene(P, seed, mode, W=64, H=64, distance=22.0, **kw):
     return d
 
 
-def oracle_forward(d, exact=True, antialiasing=False, use_cov=False):
+def oracle_forward(d, exact=True, antialiasing=False, use_cov=False, scale_modifier=1.0):
     import oracle
     cov = None
     if use_cov:
@@ -149,8 +149,79 @@ def oracle_forward(d, exact=True, antialiasing=False, use_cov=False):
         d["means3D"], d["colors"], d["opacities"], None if use_cov else d["scales"],
         None if use_cov else d["rotations"], cov, d["viewmatrix"], d["projmatrix"],
         d["image_width"], d["image_height"], d["tanfovx"], d["tanfovy"], d["bg"],
-        antialiasing=antialiasing, exact_exp=exact)
+        scale_modifier=scale_modifier, antialiasing=antialiasing, exact_exp=exact)
     return color, radii, invd, st
+
+
+# Scenes that move the operands every other test holds at their trivial value (background, scale
+# modifier, antialiasing) at small and ragged sizes: (id, kind, W, H, P, seed, xy factor, yaw, pitch,
+# opacity override, scale_modifier, antialiasing).  tests/test_oracle.py pins the oracle on them
+# against float64 autograd, tests/test_gpu_operands.py the GPU.
+OPERAND_SCENES = (
+    ("random48x32-mod0.6", "random", 48, 32, 40, 23, 0.25, 0.0, 0.0, None, 0.6, False),
+    ("random48x32-mod1.7-aa", "random", 48, 32, 40, 23, 0.25, 0.0, 0.0, None, 1.7, True),
+    ("random50x38-yaw-aa", "random", 50, 38, 150, 7, 0.15, 0.3, -0.2, None, 1.0, True),
+    ("random17x33-saturated-mod1.3", "random", 17, 33, 120, 5, 0.1, 0.0, 0.0, 0.97, 1.3, False),
+    ("avatar64x48-mod1.2-aa", "avatar", 64, 48, 400, 24, None, 0.0, 0.0, None, 1.2, True),
+    ("random1x1", "random", 1, 1, 30, 9, 0.01, 0.0, 0.0, None, 1.0, False),
+)
+
+
+def operand_scene(row):
+    """One row of OPERAND_SCENES -> (scene dict with a non-zero bg, dL[C,H,W], dLinv[1,H,W],
+    scale_modifier, antialiasing)."""
+    _, kind, W, H, P, seed, xy, yaw, pitch, opac, mod, aa = row
+    d = make_scene(kind, P, W, H, seed=seed, yaw=yaw, pitch=pitch)
+    if xy is not None:
+        d["means3D"][:, :2] *= np.float32(xy)
+    if opac is not None:
+        d["opacities"][:] = np.float32(opac)
+    rng = np.random.default_rng(3)
+    d["bg"] = rng.uniform(-1.0, 2.0, C).astype(np.float32)
+    dL = rng.normal(size=(C, H, W)).astype(np.float32)
+    dLinv = rng.normal(size=(1, H, W)).astype(np.float32)
+    return d, dL, dLinv, mod, aa
+
+
+F64_NAMES = ("colors", "opacity", "means3D", "scales", "rotations", "means2D")
+
+
+def float64_reference(d, st, dL=None, dLinv=None, scale_modifier=1.0, antialiasing=False):
+    """tests/torch_ref.py on the scene, over the tile lists of the oracle state `st`: (image
+    [C,H,W], n_contrib [H*W], gradients by F64_NAMES or None without dL), numpy float64.  "scales" is
+    the gradient w.r.t. scale_modifier * scales and "means2D" the NDC one, as the reference returns
+    them (torch_ref's docstring)."""
+    import torch
+    import torch_ref
+    W, H = d["image_width"], d["image_height"]
+    tile_lists = {t: st["point_list"][s:e] for t, (s, e) in enumerate(st["ranges"]) if e > s}
+    f64 = lambda a: torch.tensor(np.asarray(a, np.float64), requires_grad=True)  # noqa: E731
+    m3, sc, rot, op, colr = (f64(d["means3D"]), f64(d["scales"]), f64(d["rotations"]),
+                              f64(d["opacities"].reshape(-1)), f64(d["colors"]))
+    off = torch.zeros((m3.shape[0], 3), dtype=torch.float64, requires_grad=True)
+    pr = torch_ref.project(m3, sc, rot, torch.tensor(d["viewmatrix"], dtype=torch.float64),
+                           torch.tensor(d["projmatrix"], dtype=torch.float64), W, H, float(d["tanfovx"]),
+                           float(d["tanfovy"]), scale_mod=float(scale_modifier), ndc_offset=off,
+                           antialiasing=antialiasing)
+    out, inv, _, nc = torch_ref.render(pr, op * pr["o1"], colr, torch.tensor(d["bg"], dtype=torch.float64),
+                                       W, H, tile_lists)
+    grads = None
+    if dL is not None:
+        loss = ((out * torch.tensor(dL, dtype=torch.float64)).sum()
+                + (inv * torch.tensor(dLinv[0], dtype=torch.float64)).sum())
+        loss.backward()
+        zero = lambda t: torch.zeros_like(t) if t.grad is None else t.grad  # noqa: E731 (nothing rendered)
+        grads = dict(colors=zero(colr), opacity=zero(op), means3D=zero(m3), scales=zero(pr["scales_eff"]),
+                     rotations=zero(rot), means2D=zero(off)[:, :2])
+        grads = {k: v.numpy() for k, v in grads.items()}
+    return out.detach().numpy(), nc.numpy().reshape(-1), grads
+
+
+def scale_err(a, ref):
+    """max|a - ref| / max|ref|."""
+    a = np.asarray(a, np.float64)
+    ref = np.asarray(ref, np.float64)
+    return float(np.abs(a.reshape(ref.shape) - ref).max() / max(np.abs(ref).max(), 1e-30))
 
 
 def torch_inputs(d, device="cuda", requires_grad=False):
@@ -165,7 +236,7 @@ def torch_inputs(d, device="cuda", requires_grad=False):
     return t
 
 
-def gpu_forward(d, antialiasing=False, use_cov=None, debug=False, numerics=0):
+def gpu_forward(d, antialiasing=False, use_cov=None, debug=False, numerics=0, scale_modifier=1.0):
     """Runs _C.rasterize_gaussians; returns numpy outputs plus decoded scratch state."""
     import torch
     from guava_renderer_amd.diff_gaussian_rasterization_32 import _C
@@ -175,7 +246,7 @@ def gpu_forward(d, antialiasing=False, use_cov=None, debug=False, numerics=0):
     scales = t["scales"] if use_cov is None else empty
     rots = t["rotations"] if use_cov is None else empty
     R, color, radii, gb, bb, ib, invd = _C.rasterize_gaussians(
-        t["bg"], t["means3D"], t["colors"], t["opacities"], scales, rots, 1.0, cov,
+        t["bg"], t["means3D"], t["colors"], t["opacities"], scales, rots, float(scale_modifier), cov,
         t["viewmatrix"], t["projmatrix"], d["tanfovx"], d["tanfovy"], d["image_height"],
         d["image_width"], empty, 0, t["campos"], False, antialiasing, debug, numerics=numerics)
     torch.cuda.synchronize()

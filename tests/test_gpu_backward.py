@@ -16,40 +16,42 @@ pytestmark = pytest.mark.gpu
 NAMES = ("means2D", "colors", "opacity", "means3D", "cov3D", "sh", "scales", "rotations")
 
 
-def _gpu_backward(d, dL, dLinv, antialiasing=False, use_cov=None, numerics=0):
+def _gpu_backward(d, dL, dLinv, antialiasing=False, use_cov=None, numerics=0, scale_modifier=1.0):
     from guava_renderer_amd.diff_gaussian_rasterization_32 import _C
     t = torch_inputs(d)
     empty = torch.Tensor([])
     cov = empty if use_cov is None else torch.tensor(use_cov, device="cuda")
     scales = t["scales"] if use_cov is None else empty
     rots = t["rotations"] if use_cov is None else empty
+    mod = float(scale_modifier)
     R, color, radii, gb, bb, ib, invd = _C.rasterize_gaussians(
-        t["bg"], t["means3D"], t["colors"], t["opacities"], scales, rots, 1.0, cov,
+        t["bg"], t["means3D"], t["colors"], t["opacities"], scales, rots, mod, cov,
         t["viewmatrix"], t["projmatrix"], d["tanfovx"], d["tanfovy"], d["image_height"],
         d["image_width"], empty, 0, t["campos"], False, antialiasing, False, numerics=numerics)
     dLt = torch.tensor(dL, device="cuda")
     dLi = torch.tensor(dLinv, device="cuda") if dLinv is not None else torch.zeros((0, 1), device="cuda")
     grads = _C.rasterize_gaussians_backward(
-        t["bg"], t["means3D"], radii, t["colors"], t["opacities"], scales, rots, 1.0, cov,
+        t["bg"], t["means3D"], radii, t["colors"], t["opacities"], scales, rots, mod, cov,
         t["viewmatrix"], t["projmatrix"], d["tanfovx"], d["tanfovy"], dLt, dLi, empty, 0, t["campos"],
         gb, R, bb, ib, antialiasing, False, numerics=numerics)
     torch.cuda.synchronize()
     return [g.cpu().numpy() for g in grads]
 
 
-def _oracle_backward(d, dL, dLinv, antialiasing=False, use_cov=None):
+def _oracle_backward(d, dL, dLinv, antialiasing=False, use_cov=None, scale_modifier=1.0, reverse_order=False):
     import oracle
     _, _, _, st = oracle.forward(
         d["means3D"], d["colors"], d["opacities"], None if use_cov is not None else d["scales"],
         None if use_cov is not None else d["rotations"], use_cov, d["viewmatrix"], d["projmatrix"],
         d["image_width"], d["image_height"], d["tanfovx"], d["tanfovy"], d["bg"],
-        antialiasing=antialiasing)
+        scale_modifier=scale_modifier, antialiasing=antialiasing)
     return oracle.backward(st, d["means3D"], d["colors"], d["opacities"],
                            None if use_cov is not None else d["scales"],
                            None if use_cov is not None else d["rotations"], use_cov,
                            d["viewmatrix"], d["projmatrix"], d["image_width"], d["image_height"],
                            d["tanfovx"], d["tanfovy"], d["bg"], dL, dLinv,
-                           antialiasing=antialiasing)
+                           scale_modifier=scale_modifier, antialiasing=antialiasing,
+                           reverse_order=reverse_order)
 
 
 def _check(g, o, tol=1e-4, skip=()):

@@ -18,9 +18,10 @@ def _lib():
     return _lib
 
 
-def _compare_exact(d, antialiasing=False):
-    g_col, g_radii, g_inv, gs = gpu_forward(d, antialiasing=antialiasing)
-    o_col, o_radii, o_inv, os_ = oracle_forward(d, exact=True, antialiasing=antialiasing)
+def _compare_exact(d, antialiasing=False, scale_modifier=1.0):
+    g_col, g_radii, g_inv, gs = gpu_forward(d, antialiasing=antialiasing, scale_modifier=scale_modifier)
+    o_col, o_radii, o_inv, os_ = oracle_forward(d, exact=True, antialiasing=antialiasing,
+                                                scale_modifier=scale_modifier)
     P = d["means3D"].shape[0]
     np.testing.assert_array_equal(g_radii, o_radii)
     vis = o_radii > 0

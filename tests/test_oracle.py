@@ -7,11 +7,9 @@ autograd (tests/torch_ref.py) for the forward image and every gradient.
 """
 import numpy as np
 import pytest
-import torch
 
 import oracle
-from helpers import make_scene
-import torch_ref
+from helpers import F64_NAMES, OPERAND_SCENES, float64_reference, make_scene, operand_scene, scale_err
 
 C = 32
 
@@ -179,34 +177,29 @@ def test_equal_depth_ties_keep_index_order():
         assert np.all(np.diff(lst.astype(np.int64)) > 0)
 
 
-def _torch_check(d, W, H, dL=None, dLinv=None, tol_img=2e-5, tol_grad=2e-5):
-    col, radii, invd, st = _fwd(d)
-    tile_lists = {t: st["point_list"][s:e] for t, (s, e) in enumerate(st["ranges"]) if e > s}
-    f64 = lambda a: torch.tensor(np.asarray(a, np.float64), requires_grad=True)  # noqa: E731
-    m3, sc, rot, op, colr = (f64(d["means3D"]), f64(d["scales"]), f64(d["rotations"]),
-                              f64(d["opacities"].reshape(-1)), f64(d["colors"]))
-    off = torch.zeros((m3.shape[0], 3), dtype=torch.float64, requires_grad=True)
-    pr = torch_ref.project(m3, sc, rot, torch.tensor(d["viewmatrix"], dtype=torch.float64),
-                           torch.tensor(d["projmatrix"], dtype=torch.float64), W, H, float(d["tanfovx"]),
-                           float(d["tanfovy"]), ndc_offset=off)
-    out, inv, Tf, nc = torch_ref.render(pr, op, colr, torch.tensor(d["bg"], dtype=torch.float64), W, H,
-                                        tile_lists)
-    same = (nc.numpy().reshape(-1) == st["n_contrib"])
+def _torch_check(d, W, H, dL=None, dLinv=None, tol_img=2e-5, tol_grad=2e-5, scale_modifier=1.0,
+                 antialiasing=False):
+    """The oracle against tests/torch_ref.py (float64, autograd) with the scene's own d["bg"]."""
+    col, radii, invd, st = _fwd(d, scale_modifier=scale_modifier, antialiasing=antialiasing)
+    out, nc, ref = float64_reference(d, st, dL, dLinv, scale_modifier=scale_modifier, antialiasing=antialiasing)
+    same = (nc == st["n_contrib"])
+    print(f"  n_contrib agreement {same.mean():.4f}")
     assert same.mean() > 0.995, same.mean()
-    err = np.abs(out.detach().numpy() - col).reshape(C, -1)[:, same].max()
+    err = np.abs(out - col).reshape(C, -1)[:, same].max()
+    print(f"  image: {err:.3g}")
     assert err < tol_img, err
     if dL is None:
         return
-    loss = (out * torch.tensor(dL, dtype=torch.float64)).sum() + (inv * torch.tensor(dLinv[0], dtype=torch.float64)).sum()
-    loss.backward()
     g = oracle.backward(st, d["means3D"], d["colors"], d["opacities"], d["scales"], d["rotations"], None,
-                        d["viewmatrix"], d["projmatrix"], W, H, d["tanfovx"], d["tanfovy"], d["bg"], dL, dLinv)
+                        d["viewmatrix"], d["projmatrix"], W, H, d["tanfovx"], d["tanfovy"], d["bg"], dL, dLinv,
+                        scale_modifier=scale_modifier, antialiasing=antialiasing)
     g_m2, g_col, g_op, g_m3, g_cov, g_sh, g_sc, g_rot = g
-    for name, ours, ref in (("colors", g_col, colr.grad), ("opacity", g_op.reshape(-1), op.grad),
-                            ("means3D", g_m3, m3.grad), ("scales", g_sc, sc.grad),
-                            ("rotations", g_rot, rot.grad), ("means2D", g_m2[:, :2], off.grad[:, :2])):
-        ref = ref.numpy()
-        e = np.abs(ours - ref).max() / max(np.abs(ref).max(), 1e-30)
+    ours = dict(colors=g_col, opacity=g_op.reshape(-1), means3D=g_m3, scales=g_sc, rotations=g_rot,
+                means2D=g_m2[:, :2])
+    errs = {name: scale_err(ours[name], ref[name]) for name in F64_NAMES}
+    print("  oracle vs float64, of scale: " + ", ".join(f"{k} {v:.3g}" for k, v in errs.items()))
+    for name, e in errs.items():
+        assert np.abs(ref[name]).max() > 0, name
         assert e < tol_grad, (name, e)
 
 
@@ -218,6 +211,17 @@ def test_forward_and_gradients_match_float64_autograd():
     dL = rng.normal(size=(C, H, W)).astype(np.float32)
     dLinv = rng.normal(size=(1, H, W)).astype(np.float32)
     _torch_check(d, W, H, dL, dLinv)
+
+
+@pytest.mark.parametrize("row", OPERAND_SCENES, ids=[r[0] for r in OPERAND_SCENES])
+def test_operand_axes_match_float64_autograd(row):
+    """A non-zero background (the backward's -T_final (bg . dL) / (1 - alpha) term), scale_modifier
+    != 1 (dL/dscales is the gradient w.r.t. scale_modifier * scales), antialiasing (the backward
+    evaluates its closed form at the dilated covariance) and ragged / saturated / 1x1 images: the
+    oracle's image and every gradient against float64 autograd, at _torch_check's bars."""
+    d, dL, dLinv, mod, aa = operand_scene(row)
+    assert np.abs(d["bg"]).min() > 0
+    _torch_check(d, d["image_width"], d["image_height"], dL, dLinv, scale_modifier=mod, antialiasing=aa)
 
 
 def test_avatar_forward_matches_float64_restatement():

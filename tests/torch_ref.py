@@ -9,11 +9,42 @@ Reference quirks reproduced so that autograd equals the reference's hand-written
   * alpha = min(0.99, o*G) with the gradient of o*G (backward.cu:619, 635 ignore the clamp);
   * the EWA clamp of t.xy zeroes the gradient outside the limits (backward.cu:182-183);
   * dL/dmeans2D is the gradient w.r.t. the NDC position (ddelx_dx = W/2, backward.cu:527);
-  * tile membership (the discrete rect test) is taken as given.
+  * tile membership (the discrete rect test) is taken as given;
+  * dL/dscales is the gradient w.r.t. the effective scale s = scale_mod * scales, with no factor
+    scale_mod (backward.cu:347, 375-377): project() returns s as "scales_eff" with its gradient
+    retained, and that gradient is what the reference writes to dL_dscales;
+  * antialiasing: opacity * h, h = sqrt(max(0.000025, det_cov / det_cov_plus_h)) (forward.cu:216-223,
+    265); the backward's d(ratio)/d(c_xx, c_xy, c_yy) is the closed form derived for the undilated
+    entries but evaluated at the dilated c_xx + 0.3, c_yy + 0.3 (backward.cu:235-245, after
+    :213-214), and zero where the ratio is <= 0.000025 (backward.cu:220): _AAScale below.
 """
 import torch
 
 C = 32
+H_VAR = 0.3
+AA_FLOOR = 0.000025
+
+
+class _AAScale(torch.autograd.Function):
+    """h(c_xx, c_xy, c_yy) of the undilated 2D covariance, with the reference's backward."""
+
+    @staticmethod
+    def forward(ctx, cxx, cxy, cyy):
+        det = cxx * cyy - cxy * cxy
+        det_h = (cxx + H_VAR) * (cyy + H_VAR) - cxy * cxy
+        ratio = det / det_h
+        h = torch.sqrt(torch.clamp(ratio, min=AA_FLOOR))
+        ctx.save_for_backward(cxx, cxy, cyy, ratio, h)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        cxx, cxy, cyy, ratio, h = ctx.saved_tensors
+        d_inside_root = torch.where(ratio <= AA_FLOOR, torch.zeros_like(dh), dh / (2 * h))
+        x, y, z, w = cxx + H_VAR, cyy + H_VAR, cxy, H_VAR  # the dilated entries (the quirk)
+        d = d_inside_root / (w * w + w * (x + y) + x * y - z * z) ** 2
+        return (w * (w * y + y * y + z * z) * d, -2.0 * w * z * (w + x + y) * d,
+                w * (w * x + x * x + z * z) * d)
 
 
 def _glm(*a):
@@ -31,8 +62,10 @@ def _tr(A):
     return A.transpose(-1, -2)
 
 
-def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=1.0, ndc_offset=None):
-    """Per-Gaussian projection. Returns dict of tensors (float64)."""
+def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=1.0, ndc_offset=None,
+            antialiasing=False):
+    """Per-Gaussian projection. Returns dict of tensors (float64): "o1" is the factor on the opacity
+    (h under antialiasing, else 1), "scales_eff" the effective scale scale_mod * scales."""
     V = view.reshape(4, 4)
     Pm = proj.reshape(4, 4)
     p = means3D
@@ -44,6 +77,8 @@ def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=
         ndc = ndc + ndc_offset[:, :2]
     # cov3D (forward.cu:114-148)
     s = scale_mod * scales
+    if s.requires_grad:
+        s.retain_grad()
     z0 = torch.zeros_like(s[:, 0])
     o1 = torch.ones_like(s[:, 0])
     S = _glm(s[:, 0], z0, z0, z0, s[:, 1], z0, z0, z0, s[:, 2])
@@ -65,13 +100,15 @@ def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=
     Wm = _glm(*[V.reshape(-1)[k].expand_as(z0) for k in (0, 4, 8, 1, 5, 9, 2, 6, 10)])
     T = _mul(Wm, J)
     cov = _mul(_mul(_tr(T), _tr(Sig)), T)
-    cxx = cov[:, 0, 0] + 0.3
+    if antialiasing:
+        o1 = _AAScale.apply(cov[:, 0, 0], cov[:, 0, 1], cov[:, 1, 1])
+    cxx = cov[:, 0, 0] + H_VAR
     cxy = cov[:, 0, 1]
-    cyy = cov[:, 1, 1] + 0.3
+    cyy = cov[:, 1, 1] + H_VAR
     det = cxx * cyy - cxy * cxy
     conic = torch.stack([cyy / det, -cxy / det, cxx / det], -1)
     pix = ((ndc + 1.0) * torch.tensor([W, H], dtype=ndc.dtype) - 1.0) * 0.5
-    return dict(depth=tz, means2D=pix, conic=conic, cov3D=Sig, o1=o1)
+    return dict(depth=tz, means2D=pix, conic=conic, cov3D=Sig, o1=o1, scales_eff=s)
 
 
 def render(proj_out, opacities, colors, bg, W, H, tile_lists, exact_exp=None):
