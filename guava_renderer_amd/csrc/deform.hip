@@ -19,6 +19,10 @@
 //                                     (HBM-bound: 4*(NB + 9(J-1)) bytes per vertex coordinate)
 //   k_lbs_blend_mfma 3V/32 x B/32 WGs the same for B > 16 on the matrix cores (f32 MFMA), bases
 //                                     streamed once per 32 frames
+//   k_lbs_coef_tiles                  B > 16 on tiled bases: the blend's coefficient rows (pose features,
+//                                     betas) as 32-frame x 8-k tiles, in place of k_lbs_rodrigues
+//   k_lbs_blend_tiledc                the matrix-core blend on tiled bases and tiled coefficients; one
+//                                     blend or two independent ones per launch
 //   k_lbs_joints     J/4 x B WGs      J_regressor . v_shaped (+ joints_offset)
 //   k_lbs_chain      B WGs            the kinematic chain in LDS, one tree level per step
 //   k_lbs_skin       V x B            T_v = sum_j w_vj A_j, v = T_v [v_posed; 1]
@@ -350,8 +354,8 @@ __device__ __forceinline__ void blend_tiled_mfma_part(floatx16& acc, const float
 }
 
 // k_lbs_blend_mfma over the tiled bases: one workgroup per 32 coordinates x 32 frames, the same
-// wave-order reduction and epilogue.  NW waves split the k groups (g = w mod NW): 8 when the grid
-// has at most 512 workgroups (the FLAME head, 471: 4 waves per workgroup left the SIMDs under two
+// wave-order reduction and epilogue.  NW waves split the k groups (g = w mod NW): 8 when the model
+// has at most 512 coordinate tiles (blend_ksplit; the FLAME head, 471: 4 waves per workgroup left the SIMDs under two
 // waves each, every wave a long serial load -> MFMA chain), else 4.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_lbs_blend_tiled(int B, int M, int NB, int NP,
@@ -391,6 +395,166 @@ __global__ __launch_bounds__(64 * NW) void k_lbs_blend_tiled(int B, int M, int N
         v_shaped[(int64_t)b * M + m] = vs;
         if (v_posed) v_posed[(int64_t)b * M + m] = Pz + vs;
     }
+}
+
+// ---- tiled coefficients (the A operand in the base tiles' layout)
+// The B coefficient rows [B][K] of a blend as 1-KB tiles of 32 frames x 8 k: as float4
+// (bt * nkg + g) * 64 + 32 h + c, component j, the value coef[32 bt + c][8g + 4h + j], zero where the
+// frame is >= B or k >= K.  A wave's coefficient load is then one contiguous 1-KB read, like its base
+// tile: the row-major gather of blend_tiled_mfma_part touches 64 cache lines (rows >= 1,400 bytes
+// apart) for the same 1 KB, once per k-group and workgroup.  k_lbs_coef_tiles writes every word of
+// the tiles on every call (the workspace is reused; the blend reads the padding).
+__device__ __forceinline__ int64_t coef_tile_index(int nkg, int b, int k) {
+    return ((((int64_t)(b >> 5) * nkg + (k >> 3)) * 64 + 32 * ((k >> 2) & 1) + (b & 31)) << 2) + (k & 3);
+}
+
+// One model's coefficient tiles: threads [0, n_pose) take (frame of the padded 32-frame tiles, joint):
+// k_lbs_rodrigues' rotation (the same expressions) and pose feature R - I into feat_tiles, zeros for
+// the padding frames and the k tail; threads [n_pose, n_pose + n_beta) take one float4 of beta_tiles
+// from the row-major betas.
+struct CoefJob {
+    int B, J, NB, pose2rot;
+    int n_pose, n_beta;
+    const float* pose;   // null: no pose part (n_pose = 0)
+    const float* betas;  // null: no betas part (n_beta = 0)
+    float* feat_tiles;
+    float4* beta_tiles;
+};
+
+__device__ __forceinline__ void coef_tiles_one(const CoefJob& c, int idx) {
+    if (idx < c.n_pose) {
+        const int J = c.J, NP = 9 * (J - 1), nkg = (NP + 7) / 8;
+        const int b = idx / J, j = idx - b * J;
+        float R[9];
+        if (b < c.B) {
+            rodrigues_one(c.pose, idx, c.pose2rot, R);
+#pragma unroll
+            for (int e = 0; e < 9; e++) R[e] = R[e] - ((e % 4) == 0 ? 1.0f : 0.0f);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 9; e++) R[e] = 0.f;
+        }
+        if (j > 0) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) c.feat_tiles[coef_tile_index(nkg, b, 9 * (j - 1) + e)] = R[e];
+            if (j == J - 1)
+                for (int k = NP; k < 8 * nkg; k++) c.feat_tiles[coef_tile_index(nkg, b, k)] = 0.f;
+        }
+        return;
+    }
+    idx -= c.n_pose;
+    if (idx >= c.n_beta) return;
+    const int NB = c.NB, nkg = (NB + 7) / 8;
+    const int lane = idx & 63, tg = idx >> 6;
+    const int g = tg % nkg, bt = tg / nkg;
+    const int b = 32 * bt + (lane & 31), k0 = 8 * g + 4 * (lane >> 5);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = (b < c.B && k0 + j < NB) ? c.betas[(int64_t)b * NB + k0 + j] : 0.f;
+    c.beta_tiles[idx] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// the coefficient tiles of one model, or of two independent ones in one launch (EHM's FLAME head and
+// body: both depend only on the packed rows)
+__global__ __launch_bounds__(256) void k_lbs_coef_tiles(CoefJob a, CoefJob b) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int na = a.n_pose + a.n_beta;
+    if (i < na) coef_tiles_one(a, i);
+    else if (i - na < b.n_pose + b.n_beta) coef_tiles_one(b, i - na);
+}
+
+// blend_tiled_mfma_part with the coefficients read from their tiles: the same a and v operands in
+// the same order, so the same sums bit for bit; no per-lane frame / k selects in the loop.
+// One k group per round on two register sets: a round's two loads are issued before the round
+// before it multiplies.  More loads in flight per wave ran slower.
+__device__ __forceinline__ void blend_tiledc_mfma_part(floatx16& acc, const float4* __restrict__ ct,
+                                                       const float4* __restrict__ tb, int K, int t, int bt, int w,
+                                                       int lane, int nw) {
+    const int nkg = (K + 7) / 8;
+    const float4* __restrict__ p = tb + (int64_t)t * nkg * 64 + lane;
+    const float4* __restrict__ c = ct + (int64_t)bt * nkg * 64 + lane;
+    auto mma = [&](const float4& v, const float4& a) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, v.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, v.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, v.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, v.w, acc, 0, 0, 0);
+    };
+    if (w >= nkg) return;
+    float4 v0 = p[(int64_t)w * 64], a0 = c[(int64_t)w * 64], v1, a1;
+    for (int g = w; g < nkg; g += 2 * nw) {
+        const bool more = g + nw < nkg;
+        if (more) { v1 = p[(int64_t)(g + nw) * 64]; a1 = c[(int64_t)(g + nw) * 64]; }
+        mma(v0, a0);
+        if (more) {
+            if (g + 2 * nw < nkg) { v0 = p[(int64_t)(g + 2 * nw) * 64]; a0 = c[(int64_t)(g + 2 * nw) * 64]; }
+            mma(v1, a1);
+        }
+    }
+}
+
+// One batched blend over tiled bases and tiled coefficients (k_lbs_blend_tiled's arguments)
+struct BlendTJob {
+    int M, NB, NP;
+    const float* vt;
+    int64_t vt_stride;
+    const float4* beta_tiles;
+    const float4* sd_tiled;
+    const float4* feat_tiles;
+    const float4* pd_tiled;
+    float* v_shaped;
+    float* v_posed;
+};
+
+// k_lbs_blend_tiled<KS>'s arithmetic on tiled coefficients, in a workgroup of WAVES >= KS waves: each
+// group of KS waves owns one coordinate tile (tile = WAVES / KS * tw + group) of frame tile bt, splits
+// the k groups KS ways and reduces in its own wave order -- the sums of k_lbs_blend_tiled<KS>, bit
+// for bit, whatever the workgroup size.
+template <int WAVES, int KS>
+__device__ __forceinline__ void blend_tiledc_block(const BlendTJob& j, int B, int tw, int bt,
+                                                   float (*red)[2][16][64]) {
+    const int lane = threadIdx.x & 63, w8 = threadIdx.x >> 6, hi = lane >> 5, l32 = lane & 31;
+    const int sg = w8 / KS, w = w8 % KS;
+    const int M = j.M, NB = j.NB;
+    const int t = tw * (WAVES / KS) + sg;
+    const bool tok = t < (M + 31) / 32;  // (an odd tile count leaves the last workgroup's second group idle)
+    const int m = t * 32 + l32, b0 = bt * 32;
+    const bool mok = tok && m < M;
+    floatx16 as, ap;
+#pragma unroll
+    for (int r = 0; r < 16; r++) { as[r] = 0.f; ap[r] = 0.f; }
+    if (tok && NB > 0) blend_tiledc_mfma_part(as, j.beta_tiles, j.sd_tiled, NB, t, bt, w, lane, KS);
+    if (tok && j.NP > 0 && j.v_posed)
+        blend_tiledc_mfma_part(ap, j.feat_tiles, j.pd_tiled, j.NP, t, bt, w, lane, KS);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        red[w8][0][r][lane] = as[r];
+        red[w8][1][r][lane] = ap[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16 / KS; i++) {
+        const int r = (16 / KS) * w + i;
+        const int b = b0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (!mok || b >= B) continue;
+        float S = red[sg * KS][0][r][lane], Pz = red[sg * KS][1][r][lane];
+#pragma unroll
+        for (int u = 1; u < KS; u++) { S += red[sg * KS + u][0][r][lane]; Pz += red[sg * KS + u][1][r][lane]; }
+        const float tv = j.vt[(int64_t)b * j.vt_stride + m];
+        const float vs = NB > 0 ? tv + S : tv;
+        j.v_shaped[(int64_t)b * M + m] = vs;
+        if (j.v_posed) j.v_posed[(int64_t)b * M + m] = Pz + vs;
+    }
+}
+
+// One blend (na = grid.x), or two independent ones in one launch (EHM's FLAME head blend beside the
+// body's shape blend, the batched k_lbs_blend_tiled1_pair): workgroups [0, na) take job a with a
+// KSA-way k split, the rest job b with KSB; blockIdx.y is the 32-frame tile.  Neither job reads what
+// the other writes.
+template <int WAVES, int KSA, int KSB>
+__global__ __launch_bounds__(64 * WAVES) void k_lbs_blend_tiledc(int B, BlendTJob a, int na, BlendTJob b) {
+    __shared__ float red[WAVES][2][16][64];
+    if ((int)blockIdx.x < na) blend_tiledc_block<WAVES, KSA>(a, B, blockIdx.x, blockIdx.y, red);
+    else blend_tiledc_block<WAVES, KSB>(b, B, blockIdx.x - na, blockIdx.y, red);
 }
 
 // One frame over the tiled bases (the per-frame drop-in path): lane (c, h) of wave w sums
@@ -515,6 +679,15 @@ bool blend_tiled1_applies(int B, int NB, int NP, const float* vp, const GsrLbsSp
            (NB > 0 || (NP > 0 && vp));
 }
 
+// the k split of a matrix-core blend over M coordinates on tiled bases: 8 waves per tile for at most
+// 512 coordinate tiles (the FLAME head, 471), else 4 -- by the model alone, on every path, so a
+// frame's sums depend neither on the batch it came in nor on the entry point (the choice was by the
+// whole grid before: the same split up to 32 frames)
+static int blend_ksplit(int M) {
+    static const int nw_env = tune_env("GSR_BLEND_NW", 0);
+    return nw_env == 4 || nw_env == 8 ? nw_env : ((M + 31) / 32 <= 512 ? 8 : 4);
+}
+
 static void launch_blend(int B, int M, int NB, int NP, const float* vt, int64_t vt_stride, const float* betas,
                          const float* sd_t, const float* feat, const float* pd, float* vs, float* vp,
                          hipStream_t s, const GsrLbsSparse* sp, const float* pose, int pose2rot) {
@@ -524,9 +697,8 @@ static void launch_blend(int B, int M, int NB, int NP, const float* vt, int64_t 
     const bool tiled = tiled_on && sp && (NB == 0 || sp->shapedirs_tiled) &&
                        (NP == 0 || !vp || sp->posedirs_tiled) && (NB > 0 || (NP > 0 && vp));
     if (tiled && B > kLbsFrames && !valu_only) {
-        static const int nw_env = tune_env("GSR_BLEND_NW", 0);
         const dim3 grid((M + 31) / 32, (B + 31) / 32);
-        const int nw = nw_env == 4 || nw_env == 8 ? nw_env : (grid.x * grid.y <= 512 ? 8 : 4);
+        const int nw = blend_ksplit(M);
         const float4* sdt = reinterpret_cast<const float4*>(sp->shapedirs_tiled);
         const float4* pdt = reinterpret_cast<const float4*>(sp->posedirs_tiled);
         if (nw == 8)
@@ -672,51 +844,66 @@ __global__ __launch_bounds__(256) void k_lbs_joints_csr(int B, int V, int J, con
 // jrow != null (single frame, CSR regressor): the rest joints are regressed here first -- each of the
 // 16 waves takes joints w, w + 16, ... with k_lbs_joints_csr's per-lane chains and xor tree (the same
 // sums, bit for bit) -- and written to `joints`, one launch fewer per lbs call.
+// At B > 1 the same per frame (workgroup b: frame b's v_shaped, offsets and joints).
+// nchain < gridDim.x: the workgroups past the chains only regress joints -- frame (blockIdx.x - nchain)
+// of another model, xj (EHM's unspliced body template beside the FLAME head's chain: its inputs are
+// ready at the same point).  They read nothing a chain workgroup writes, and the reverse.
 struct ChainJoints {
     const int32_t* row;
     const int32_t* col;
     const float* val;
-    const float* vs;    // v_shaped of the frame
-    const float* joff;  // or null
+    const float* vs;    // v_shaped [B][V][3]
+    const float* joff;  // [B][J][3], or null
+    float* joints;      // [B][J][3] out
+    int V, J;
 };
+// the rest joints of frame b, k_lbs_joints_csr's sums: the workgroup's 16 waves take joints w, w + 16, ...
+__device__ __forceinline__ void chain_regress_joints(const ChainJoints& cj, int b, int t, float* sjt) {
+    const int w = t >> 6, lane = t & 63;
+    const float* vs = cj.vs + (int64_t)b * cj.V * 3;
+    for (int j = w; j < cj.J; j += 16) {
+        float x = 0.f, y = 0.f, z = 0.f;
+        for (int k = cj.row[j] + lane; k < cj.row[j + 1]; k += 64) {
+            const int v = cj.col[k];
+            const float wv = cj.val[k];
+            x = fmaf(wv, vs[3 * v], x);
+            y = fmaf(wv, vs[3 * v + 1], y);
+            z = fmaf(wv, vs[3 * v + 2], z);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            x += __shfl_xor(x, off);
+            y += __shfl_xor(y, off);
+            z += __shfl_xor(z, off);
+        }
+        if (lane < 3) {
+            float v = lane == 0 ? x : lane == 1 ? y : z;
+            if (cj.joff) v = v + cj.joff[((int64_t)b * cj.J + j) * 3 + lane];
+            if (sjt) sjt[3 * j + lane] = v;
+            cj.joints[((int64_t)b * cj.J + j) * 3 + lane] = v;
+        }
+    }
+}
 __global__ __launch_bounds__(16 * GSR_LBS_MAX_JOINTS) void k_lbs_chain(int J, Parents par,
                                                                      const float* __restrict__ rot,
-                                                                     float* __restrict__ joints,
+                                                                     const float* __restrict__ joints,
                                                                      float* __restrict__ jtrans,
                                                                      float* __restrict__ A,
                                                                      const float* __restrict__ pose, int pose2rot,
-                                                                     ChainJoints cj) {
+                                                                     ChainJoints cj, int nchain, ChainJoints xj) {
     __shared__ float tm[GSR_LBS_MAX_JOINTS][16];
     __shared__ float ch[GSR_LBS_MAX_JOINTS][16];
     __shared__ int depth[GSR_LBS_MAX_JOINTS];
     __shared__ float sjt[GSR_LBS_MAX_JOINTS * 3];
     __shared__ int maxd;
     const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= nchain) {  // (the whole workgroup, before any barrier)
+        chain_regress_joints(xj, b - nchain, t, nullptr);
+        return;
+    }
     const float* Jb = joints + (int64_t)b * J * 3;
     if (cj.row) {
-        const int w = t >> 6, lane = t & 63;
-        for (int j = w; j < J; j += 16) {
-            float x = 0.f, y = 0.f, z = 0.f;
-            for (int k = cj.row[j] + lane; k < cj.row[j + 1]; k += 64) {
-                const int v = cj.col[k];
-                const float wv = cj.val[k];
-                x = fmaf(wv, cj.vs[3 * v], x);
-                y = fmaf(wv, cj.vs[3 * v + 1], y);
-                z = fmaf(wv, cj.vs[3 * v + 2], z);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                x += __shfl_xor(x, off);
-                y += __shfl_xor(y, off);
-                z += __shfl_xor(z, off);
-            }
-            if (lane < 3) {
-                float v = lane == 0 ? x : lane == 1 ? y : z;
-                if (cj.joff) v = v + cj.joff[j * 3 + lane];
-                sjt[3 * j + lane] = v;
-                joints[j * 3 + lane] = v;
-            }
-        }
+        chain_regress_joints(cj, b, t, sjt);
         __syncthreads();
         Jb = sjt;
     }
@@ -1205,9 +1392,13 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct LbsArena {
     float *rot, *feat, *vs, *vp, *joints, *A;
+    float *beta_tiles, *feat_tiles;  // the matrix-core blend's coefficient tiles (B > kLbsFrames)
 };
 
-size_t carve_lbs(char* base, int B, int V, int J, LbsArena* a) {
+size_t coef_tile_floats(int B, int K) { return (size_t)((B + 31) / 32) * (size_t)((K + 7) / 8) * 256; }
+
+// (the tiles come last: lbs_skin_splice carves without NB for A and v_posed)
+size_t carve_lbs(char* base, int B, int V, int J, int NB, LbsArena* a) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
         char* p = base ? base + off : nullptr;
@@ -1222,6 +1413,8 @@ size_t carve_lbs(char* base, int B, int V, int J, LbsArena* a) {
     t.vp = take(f * (size_t)B * V * 3);
     t.joints = take(f * (size_t)B * J * 3);
     t.A = take(f * (size_t)B * J * 16);
+    t.beta_tiles = take(f * coef_tile_floats(B, NB > 0 ? NB : 0));
+    t.feat_tiles = take(f * coef_tile_floats(B, 9 * (J - 1)));
     if (a) *a = t;
     return off;
 }
@@ -1256,9 +1449,8 @@ __global__ __launch_bounds__(256) void k_lbs_tile_base(int K, int M, int64_t n4,
 extern "C" {
 
 size_t gsr_lbs_workspace_bytes(int B, int V, int J, int NB) {
-    (void)NB;
     if (B <= 0 || V <= 0 || J <= 0) return 0;
-    return carve_lbs(nullptr, B, V, J, nullptr);
+    return carve_lbs(nullptr, B, V, J, NB, nullptr);
 }
 
 }  // extern "C"
@@ -1319,6 +1511,91 @@ int gsr_lbs_sp(int B, int V, int J, int NB, const float* v_template, int64_t v_t
 
 }  // extern "C"
 
+namespace gsr {
+namespace {
+// whether the matrix-core blend of these arguments runs on coefficient tiles (k_lbs_blend_tiledc);
+// GSR_BLEND_COEF_TILES=0: the row-major gathers of k_lbs_blend_tiled (A/B)
+bool blend_tiledc_applies(int B, int NB, int NP, const float* vp, const GsrLbsSparse* sp) {
+    static const bool on = tune_env("GSR_BLEND_TILED", 1) != 0 && tune_env("GSR_BLEND_VALU", 0) != 1 &&
+                           tune_env("GSR_BLEND_COEF_TILES", 1) != 0;
+    return on && B > kLbsFrames && sp && (NB == 0 || sp->shapedirs_tiled) &&
+           (NP == 0 || !vp || sp->posedirs_tiled) && (NB > 0 || (NP > 0 && vp));
+}
+
+CoefJob coef_job(int B, int J, int NB, const float* pose, int pose2rot, const float* betas, const LbsArena& a,
+                 float* beta_tiles) {
+    CoefJob c{};
+    c.B = B; c.J = J; c.NB = betas ? NB : 0; c.pose2rot = pose2rot;
+    c.n_pose = (pose && J > 1) ? (B + 31) / 32 * 32 * J : 0;
+    c.n_beta = c.NB > 0 ? (int)(coef_tile_floats(B, c.NB) / 4) : 0;
+    c.pose = pose; c.betas = betas;
+    c.feat_tiles = a.feat_tiles;
+    c.beta_tiles = reinterpret_cast<float4*>(beta_tiles);
+    return c;
+}
+
+void launch_coef_tiles(const CoefJob& a, const CoefJob& b, hipStream_t s) {
+    const int n = a.n_pose + a.n_beta + b.n_pose + b.n_beta;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_lbs_coef_tiles, dim3((n + 255) / 256), dim3(256), 0, s, a, b);
+}
+
+BlendTJob blendt_job(int M, int NB, int NP, const float* vt, int64_t vt_stride, const float* beta_tiles,
+                     const float* feat_tiles, float* vs, float* vp, const GsrLbsSparse* sp) {
+    return BlendTJob{M, NB, vp ? NP : 0, vt, vt_stride, reinterpret_cast<const float4*>(beta_tiles),
+                     reinterpret_cast<const float4*>(sp->shapedirs_tiled), reinterpret_cast<const float4*>(feat_tiles),
+                     reinterpret_cast<const float4*>(sp->posedirs_tiled), vs, vp};
+}
+
+// one blend, or (b != null) two independent ones in one launch
+void launch_blend_tiledc(int B, const BlendTJob& a, const BlendTJob* b, hipStream_t s) {
+    const int ka = blend_ksplit(a.M), kb = b ? blend_ksplit(b->M) : ka;
+    const int waves = ka > kb ? ka : kb;
+    const int na = ((a.M + 31) / 32 + waves / ka - 1) / (waves / ka);
+    const int nb = b ? ((b->M + 31) / 32 + waves / kb - 1) / (waves / kb) : 0;
+    const dim3 grid(na + nb, (B + 31) / 32);
+    const BlendTJob jb = b ? *b : a;
+#define GSR_BTC(W, KA, KB) \
+    hipLaunchKernelGGL((k_lbs_blend_tiledc<W, KA, KB>), grid, dim3(64 * W), 0, s, B, a, na, jb)
+    if (ka == 4 && kb == 4) GSR_BTC(4, 4, 4);
+    else if (ka == 8 && kb == 8) GSR_BTC(8, 8, 8);
+    else if (ka == 8) GSR_BTC(8, 8, 4);
+    else GSR_BTC(8, 4, 8);
+#undef GSR_BTC
+}
+
+int make_parents(int J, const int32_t* parents_host, Parents* par) {
+    for (int i = 0; i < GSR_LBS_MAX_JOINTS; i++) par->p[i] = -1;
+    if (parents_host[0] != -1) return api_fail(GSR_ERR_ARG, "gsr_lbs: parents[0] must be -1");
+    for (int i = 1; i < J; i++) {
+        if (parents_host[i] < 0 || parents_host[i] >= i)
+            return api_fail(GSR_ERR_ARG, "gsr_lbs: parents must satisfy 0 <= parents[i] < i");
+        par->p[i] = (int8_t)parents_host[i];
+    }
+    return 0;
+}
+
+void launch_skin(int B, int V, int J, const float* lbs_weights_t, const GsrLbsSparse* sp, const float* A,
+                 const float* vp, float* verts, float* vert_transforms, hipStream_t s) {
+    if (sp && sp->skin_k > 0) {
+        const dim3 g((V + 255) / 256, B);
+        if (sp->skin_k <= 4)
+            hipLaunchKernelGGL(k_lbs_skin_ell<4>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
+                               sp->skin_weight, A, vp, verts, vert_transforms);
+        else if (sp->skin_k <= 8)
+            hipLaunchKernelGGL(k_lbs_skin_ell<8>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
+                               sp->skin_weight, A, vp, verts, vert_transforms);
+        else
+            hipLaunchKernelGGL(k_lbs_skin_ell<16>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
+                               sp->skin_weight, A, vp, verts, vert_transforms);
+    } else {
+        hipLaunchKernelGGL(k_lbs_skin, dim3((V + 255) / 256, B), dim3(256), 0, s, V, J, lbs_weights_t, A, vp, verts,
+                           vert_transforms);
+    }
+}
+}  // namespace
+}  // namespace gsr
+
 // gsr_lbs_sp, or (skin = false) everything up to the skinning: the joint transforms A and v_posed stay
 // in the workspace (lbs_skin_splice reads them)
 int gsr::lbs_run(int B, int V, int J, int NB, const float* v_template, int64_t v_template_stride,
@@ -1343,16 +1620,10 @@ int gsr::lbs_run(int B, int V, int J, int NB, const float* v_template, int64_t v
         NB = 0;
     }
     Parents par;
-    for (int i = 0; i < GSR_LBS_MAX_JOINTS; i++) par.p[i] = -1;
-    if (parents_host[0] != -1) return api_fail(GSR_ERR_ARG, "gsr_lbs: parents[0] must be -1");
-    for (int i = 1; i < J; i++) {
-        if (parents_host[i] < 0 || parents_host[i] >= i)
-            return api_fail(GSR_ERR_ARG, "gsr_lbs: parents must satisfy 0 <= parents[i] < i");
-        par.p[i] = (int8_t)parents_host[i];
-    }
+    if (int rc = make_parents(J, parents_host, &par)) return rc;
     hipStream_t s = (hipStream_t)stream;
     LbsArena a;
-    carve_lbs(workspace, B, V, J, &a);
+    carve_lbs(workspace, B, V, J, NB, &a);
     float* vs = v_shaped ? v_shaped : a.vs;
     float* jr = joints ? joints : a.joints;
     float* A = joint_transforms ? joint_transforms : a.A;
@@ -1363,12 +1634,21 @@ int gsr::lbs_run(int B, int V, int J, int NB, const float* v_template, int64_t v
     // single frame on tiled bases: Rodrigues runs inside the blend (pose features) and the chain
     // (rotations), one launch fewer on the per-frame path; otherwise its own launch feeds both
     const bool fused = blend_takes_pose(B, NB, NP, a.vp, sp);
-    if (!fused) {
+    // more than kLbsFrames frames on tiled bases: the launch before the blend writes the coefficient
+    // tiles (pose features, and the caller's row-major betas re-laid) and the chain forms its rotations
+    const bool tilec = blend_tiledc_applies(B, NB, NP, a.vp, sp);
+    if (tilec) {
+        launch_coef_tiles(coef_job(B, J, NB, pose, pose2rot, betas, a, a.beta_tiles), CoefJob{}, s);
+        if (int rc = hip_check("lbs_coef_tiles")) return rc;
+    } else if (!fused) {
         hipLaunchKernelGGL(k_lbs_rodrigues, dim3((B * J + 255) / 256), dim3(256), 0, s, B, J, pose,
                            pose2rot, a.rot, a.feat);
         if (int rc = hip_check("lbs_rodrigues")) return rc;
     }
-    if (companion && companion_done && blend_tiled1_applies(B, NB, NP, a.vp, sp)) {
+    if (tilec) {
+        const BlendTJob j = blendt_job(M, NB, NP, v_template, v_template_stride, a.beta_tiles, a.feat_tiles, vs, a.vp, sp);
+        launch_blend_tiledc(B, j, nullptr, s);
+    } else if (companion && companion_done && blend_tiled1_applies(B, NB, NP, a.vp, sp)) {
         // this blend and the caller's independent one in one launch (k_lbs_blend_tiled1_pair)
         const Blend1Job ja = blend1_job(M, NB, NP, v_template, betas, a.feat, vs, a.vp, sp, fused ? pose : nullptr,
                                         pose2rot);
@@ -1382,33 +1662,102 @@ int gsr::lbs_run(int B, int V, int J, int NB, const float* v_template, int64_t v
     if (int rc = hip_check("lbs_blend")) return rc;
     // single frame with the CSR regressor: the joints are regressed inside the chain's workgroup
     // (GSR_CHAIN_JOINTS=0: their own launch, A/B)
+    // and on the coefficient-tile path (more than kLbsFrames frames); 1 < B <= kLbsFrames keeps its
+    // launches (GSR_CHAIN_BATCH=0: only for single frames, as before, A/B)
     static const bool chain_joints_on = tune_env("GSR_CHAIN_JOINTS", 1) != 0;
-    ChainJoints cj{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (B == 1 && sp && sp->jreg_row && chain_joints_on) {
-        cj = ChainJoints{sp->jreg_row, sp->jreg_col, sp->jreg_val, vs, joints_offset};
+    static const bool chain_batch_on = tune_env("GSR_CHAIN_BATCH", 1) != 0;
+    ChainJoints cj{};
+    if ((B == 1 || (tilec && chain_batch_on)) && sp && sp->jreg_row && chain_joints_on) {
+        cj = ChainJoints{sp->jreg_row, sp->jreg_col, sp->jreg_val, vs, joints_offset, jr, V, J};
     } else {
         launch_joints(B, V, J, J_regressor, sp, vs, joints_offset, jr, s);
         if (int rc = hip_check("lbs_joints")) return rc;
     }
-    hipLaunchKernelGGL(k_lbs_chain, dim3(B), dim3(16 * GSR_LBS_MAX_JOINTS), 0, s, J, par, fused ? nullptr : a.rot,
-                       jr, joints_transformed, A, pose, pose2rot, cj);
+    hipLaunchKernelGGL(k_lbs_chain, dim3(B), dim3(16 * GSR_LBS_MAX_JOINTS), 0, s, J, par,
+                       (fused || tilec) ? nullptr : a.rot, jr, joints_transformed, A, pose, pose2rot, cj, B,
+                       ChainJoints{});
     if (int rc = hip_check("lbs_chain")) return rc;
     if (!skin) return 0;
-    if (sp && sp->skin_k > 0) {
-        const dim3 g((V + 255) / 256, B);
-        if (sp->skin_k <= 4)
-            hipLaunchKernelGGL(k_lbs_skin_ell<4>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
-                               sp->skin_weight, A, a.vp, verts, vert_transforms);
-        else if (sp->skin_k <= 8)
-            hipLaunchKernelGGL(k_lbs_skin_ell<8>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
-                               sp->skin_weight, A, a.vp, verts, vert_transforms);
-        else
-            hipLaunchKernelGGL(k_lbs_skin_ell<16>, g, dim3(256), 0, s, V, J, sp->skin_k, sp->skin_joint,
-                               sp->skin_weight, A, a.vp, verts, vert_transforms);
+    launch_skin(B, V, J, lbs_weights_t, sp, A, a.vp, verts, vert_transforms, s);
+    return hip_check("lbs_skin");
+}
+
+bool gsr::ehm_batch_applies(int B, const GsrLbsSparse* sp_h, const GsrLbsSparse* sp_b, int NBh, int NBb) {
+    // GSR_EHM_BATCH=0: the per-call path (lbs_run, blend_joints_run, lbs_skin_splice, gsr_lbs_sp), A/B
+    static const bool on = tune_env("GSR_EHM_BATCH", 1) != 0 && tune_env("GSR_CHAIN_JOINTS", 1) != 0 &&
+                           tune_env("GSR_CHAIN_BATCH", 1) != 0 && tune_env("GSR_EHM_SKIN_SPLICE", 1) != 0;
+    if (!on || !sp_h || !sp_b || NBh <= 0 || NBb <= 0) return false;
+    auto ok = [&](const GsrLbsSparse* sp, int NB) {
+        return sp->jreg_row && sp->skin_k > 0 && sp->shapedirs_tiled && sp->posedirs_tiled &&
+               blend_tiledc_applies(B, NB, 0, nullptr, sp);
+    };
+    return ok(sp_h, NBh) && ok(sp_b, NBb);
+}
+
+size_t gsr::lbs_coef_tile_bytes(int B, int K) { return sizeof(float) * coef_tile_floats(B, K); }
+
+int gsr::ehm_batch_run(int B, const EhmBatchModel& head, const EhmBatchModel& body, float* body_betas_tiles,
+                       float* head_joints_t, float* body_vt, float* body_tj, const float* joints_offset,
+                       const int32_t* head_index, const float* r_eyelid, const float* l_eyelid,
+                       const float* eyelid, const float* head_scale, int hj0, int hj1, int bj0, int bj1,
+                       uint32_t* bad_index_flag, float* verts, float* joints_transformed, float* joints,
+                       float* vert_transforms, float* joint_transforms, void* stream) {
+    const int Vh = head.V, Jh = head.J, Vb = body.V, Jb = body.J;
+    if (int rc = check_sparse(head.sp, Jh, head.NB, Vh, "gsr_ehm_forward")) return rc;
+    if (int rc = check_sparse(body.sp, Jb, body.NB, Vb, "gsr_ehm_forward")) return rc;
+    if (hj0 < 0 || hj1 <= hj0 || hj1 > Jh || bj0 < 0 || bj1 <= bj0 || bj1 > Jb)
+        return api_fail(GSR_ERR_ARG, "gsr_ehm_forward: bad reference joint ranges");
+    if (eyelid && (!r_eyelid || !l_eyelid)) return api_fail(GSR_ERR_ARG, "gsr_ehm_forward: eyelid bases missing");
+    Parents par_h, par_b;
+    if (int rc = make_parents(Jh, head.parents_host, &par_h)) return rc;
+    if (int rc = make_parents(Jb, body.parents_host, &par_b)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    LbsArena ah, ab;
+    carve_lbs(head.ws, B, Vh, Jh, head.NB, &ah);
+    carve_lbs(body.ws, B, Vb, Jb, 0, &ab);
+    const int NPh = 9 * (Jh - 1), NPb = 9 * (Jb - 1);
+    float* jb = joints ? joints : ab.joints;
+    float* Ab = joint_transforms ? joint_transforms : ab.A;
+    // 2. the coefficient tiles of both models: FLAME betas + pose features, body betas + pose features
+    launch_coef_tiles(coef_job(B, Jh, head.NB, head.pose, 1, head.betas, ah, ah.beta_tiles),
+                      coef_job(B, Jb, body.NB, body.pose, 1, body.betas, ab, body_betas_tiles), s);
+    if (int rc = hip_check("ehm_coef_tiles")) return rc;
+    // 3. FLAME shape + pose blend beside the body template's shape blend
+    const BlendTJob jh = blendt_job(Vh * 3, head.NB, NPh, head.v_template, head.vt_stride, ah.beta_tiles,
+                                    ah.feat_tiles, ah.vs, ah.vp, head.sp);
+    const BlendTJob jt = blendt_job(Vb * 3, body.NB, 0, body.v_template, body.vt_stride, body_betas_tiles, nullptr,
+                                    body_vt, nullptr, body.sp);
+    static const bool pair_on = tune_env("GSR_EHM_BATCH_PAIR", 1) != 0;  // 0: two launches (A/B)
+    if (pair_on) {
+        launch_blend_tiledc(B, jh, &jt, s);
     } else {
-        hipLaunchKernelGGL(k_lbs_skin, dim3((V + 255) / 256, B), dim3(256), 0, s, V, J, lbs_weights_t, A,
-                           a.vp, verts, vert_transforms);
+        launch_blend_tiledc(B, jh, nullptr, s);
+        launch_blend_tiledc(B, jt, nullptr, s);
     }
+    if (int rc = hip_check("ehm_blend_pair")) return rc;
+    // 4. FLAME chain with its joints; further workgroups regress the unspliced body template's joints
+    const ChainJoints cjh{head.sp->jreg_row, head.sp->jreg_col, head.sp->jreg_val, ah.vs, nullptr, ah.joints, Vh, Jh};
+    const ChainJoints cjt{body.sp->jreg_row, body.sp->jreg_col, body.sp->jreg_val, body_vt, joints_offset, body_tj,
+                          Vb, Jb};
+    hipLaunchKernelGGL(k_lbs_chain, dim3(2 * B), dim3(16 * GSR_LBS_MAX_JOINTS), 0, s, Jh, par_h, nullptr, ah.joints,
+                       head_joints_t, ah.A, head.pose, 1, cjh, B, cjt);
+    if (int rc = hip_check("ehm_head_chain")) return rc;
+    // 5. head skinning + splice into the body template
+    if (int rc = lbs_skin_splice(B, Vh, Jh, head.sp, head.ws, Vb, head_index, r_eyelid, l_eyelid, eyelid, head_scale,
+                                 head_joints_t, hj0, hj1, body_tj, Jb, bj0, bj1, body_vt, bad_index_flag, stream))
+        return rc;
+    // 6. body pose blend (lbs_wobeta: v_shaped is the spliced template)
+    const BlendTJob jp = blendt_job(Vb * 3, 0, NPb, body_vt, (int64_t)Vb * 3, nullptr, ab.feat_tiles, ab.vs, ab.vp,
+                                    body.sp);
+    launch_blend_tiledc(B, jp, nullptr, s);
+    if (int rc = hip_check("ehm_body_blend")) return rc;
+    // 7. body chain with its joints
+    const ChainJoints cjb{body.sp->jreg_row, body.sp->jreg_col, body.sp->jreg_val, ab.vs, joints_offset, jb, Vb, Jb};
+    hipLaunchKernelGGL(k_lbs_chain, dim3(B), dim3(16 * GSR_LBS_MAX_JOINTS), 0, s, Jb, par_b, nullptr, jb,
+                       joints_transformed, Ab, body.pose, 1, cjb, B, ChainJoints{});
+    if (int rc = hip_check("ehm_body_chain")) return rc;
+    // 8. skin
+    launch_skin(B, Vb, Jb, nullptr, body.sp, Ab, ab.vp, verts, vert_transforms, s);
     return hip_check("lbs_skin");
 }
 
@@ -1487,7 +1836,7 @@ int gsr::lbs_skin_splice(int B, int Vh, int Jh, const GsrLbsSparse* sp_h, const 
         return api_fail(GSR_ERR_ARG, "gsr_ehm_forward: bad reference joint ranges");
     if (eyelid && (!r_eyelid || !l_eyelid)) return api_fail(GSR_ERR_ARG, "gsr_ehm_forward: eyelid bases missing");
     LbsArena a;
-    carve_lbs(const_cast<char*>(ws_h), B, Vh, Jh, &a);
+    carve_lbs(const_cast<char*>(ws_h), B, Vh, Jh, 0, &a);
     const dim3 g((Vh + 255) / 256, B);
     hipStream_t s = (hipStream_t)stream;
 #define GSR_SKS(KM)                                                                                              \

@@ -23,6 +23,30 @@ struct Blend1Job {
 bool blend_tiled1_applies(int B, int NB, int NP, const float* vp, const GsrLbsSparse* sp);
 Blend1Job blend1_job(int M, int NB, int NP, const float* vt, const float* betas, const float* feat, float* vs,
                      float* vp, const GsrLbsSparse* sp, const float* pose, int pose2rot);
+// One model's share of gsr_ehm_forward's batched path (B > 16 frames, tiled bases, CSR regressor)
+struct EhmBatchModel {
+    int V, J, NB;
+    const float* v_template;  // [V,3], or [B,V,3] when vt_stride != 0
+    int64_t vt_stride;
+    const float* betas;  // [B,NB] row-major (packed rows), or null
+    const float* pose;   // [B,J,3] axis-angle
+    const int32_t* parents_host;
+    const GsrLbsSparse* sp;
+    char* ws;  // the model's lbs workspace
+};
+// whether ehm_batch_run takes this call (else the per-call path: lbs_run, blend_joints_run, ...)
+bool ehm_batch_applies(int B, const GsrLbsSparse* sp_h, const GsrLbsSparse* sp_b, int NBh, int NBb);
+// gsr_ehm_forward after the pack launch for B > 16: Rodrigues / coefficient tiles of both models,
+// paired blend, FLAME chain (+ its joints, + the body template's joints), skin-splice, body pose
+// blend, body chain (+ joints), skin.  body_betas_tiles: workspace of gsr_lbs_coef_tile_bytes(B, NBb).
+int ehm_batch_run(int B, const EhmBatchModel& head, const EhmBatchModel& body, float* body_betas_tiles,
+                  float* head_joints_t, float* body_vt, float* body_tj, const float* joints_offset,
+                  const int32_t* head_index, const float* r_eyelid, const float* l_eyelid, const float* eyelid,
+                  const float* head_scale, int hj0, int hj1, int bj0, int bj1, uint32_t* bad_index_flag,
+                  float* verts, float* joints_transformed, float* joints, float* vert_transforms,
+                  float* joint_transforms, void* stream);
+// bytes of the tiled copy of B coefficient rows of width K (the matrix-core blend's A operand)
+size_t lbs_coef_tile_bytes(int B, int K);
 // gsr_blend_joints_sp; blend_done: its blend was launched already (as lbs_run's companion)
 int blend_joints_run(int B, int V, int J, int NB, const float* v_template, int64_t v_template_stride,
                      const float* betas, const float* shapedirs_t, const float* J_regressor,

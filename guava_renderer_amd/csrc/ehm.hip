@@ -40,6 +40,7 @@ struct EhmArena {
     float *betas_h, *pose_h, *betas_b, *pose_b, *hscale, *eyelid, *joff;
     float *hv, *hj, *vt, *tj;
     char *ws_h, *ws_b;
+    float* betas_b_tiles;  // the body template's shape coefficients as tiles (B > 16, ehm_batch_run)
 };
 
 size_t carve_ehm(char* base, const GsrEhm& e, int B, EhmArena* a) {
@@ -65,6 +66,7 @@ size_t carve_ehm(char* base, const GsrEhm& e, int B, EhmArena* a) {
     t.tj = tf(b * e.body.J * 3);
     t.ws_h = take(gsr_lbs_workspace_bytes(B, e.flame.V, e.flame.J, e.flame.NB));
     t.ws_b = take(gsr_lbs_workspace_bytes(B, e.body.V, e.body.J, 0));
+    t.betas_b_tiles = reinterpret_cast<float*>(take(lbs_coef_tile_bytes(B, e.body.NB)));
     if (a) *a = t;
     return off;
 }
@@ -208,6 +210,18 @@ int gsr_ehm_forward(const GsrEhm* ehm, int B, const GsrEhmParam* params, const G
     if (hipError_t err = hipGetLastError(); err != hipSuccess)
         return api_fail(GSR_ERR_HIP, (std::string("ehm_pack: ") + hipGetErrorString(err)).c_str());
 
+    // more than 16 frames (matrix-core blends) on tiled bases and sparse assets: the fused launch
+    // order of ehm_batch_run, 7 launches after the pack
+    if (ehm_batch_applies(B, e.flame.sparse, e.body.sparse, NBh, NBb)) {
+        const EhmBatchModel mh{Vh, Jh, NBh, e.flame.v_template, 0, a.betas_h, a.pose_h, e.flame.parents_host,
+                               e.flame.sparse, a.ws_h};
+        const EhmBatchModel mb{Vb, Jb, NBb, e.body.v_template, 0, a.betas_b, a.pose_b, e.body.parents_host,
+                               e.body.sparse, a.ws_b};
+        return ehm_batch_run(B, mh, mb, a.betas_b_tiles, a.hj, a.vt, a.tj, joff, e.head_index, e.r_eyelid,
+                             e.l_eyelid, eyelid, hscale, e.hj0, e.hj1, e.bj0, e.bj1, e.bad_index_flag, out->vertices,
+                             out->joints_transform, out->joints, out->ver_transform_mat, out->joint_transform_mat,
+                             stream);
+    }
     // FLAME head lbs (EHM.py:67-70): posed joints, and the head vertices unless the skinning is fused
     // into the splice below (ELL weights; GSR_EHM_SKIN_SPLICE=0: separate, A/B)
     static const bool skin_splice_on = tune_env("GSR_EHM_SKIN_SPLICE", 1) != 0;

@@ -44,7 +44,9 @@ extern "C" {
 #define GSR_LBS_MAX_JOINTS 64
 
 /* Scratch bytes for gsr_lbs (rotation matrices, pose features, v_shaped, v_posed, rest joints,
- * joint transforms of B frames). */
+ * joint transforms of B frames, and the NB shape coefficients and 9(J-1) pose features of the
+ * frames as 32-frame x 8-k tiles, the matrix-core blend's operand).  NB: the betas width the call
+ * will pass (0 without betas). */
 size_t gsr_lbs_workspace_bytes(int B, int V, int J, int NB);
 
 /* lbs / lbs_wobeta for B frames.
@@ -235,7 +237,7 @@ typedef struct {
     float* joint_transform_mat;   /* [B,Jb,16] */
 } GsrEhmOutputs;
 /* Scratch bytes of gsr_ehm_forward for B frames (coefficient rows, the head's vertices and joints,
- * the body template and joints, and both lbs workspaces). */
+ * the body template and joints, both lbs workspaces, and the body shape coefficients as tiles). */
 size_t gsr_ehm_workspace_bytes(const GsrEhm* ehm, int B);
 /* Column layout (EHM.py): FLAME betas = shape ++ expression ++ zeros (flame.NB wide); FLAME pose =
  * 0 global, 0 neck, jaw at column 6, eyes at 9 (3 * flame.J wide); body betas = shape (cut to
