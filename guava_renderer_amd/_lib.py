@@ -23,6 +23,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_scratch_geometry", "gsr_scratch_binning", "gsr_scratch_image", "gsr_forward_batch_deformed",
            "gsr_splice_head",
            "gsr_pack_rows", "gsr_deform_gaussians", "gsr_ehm_workspace_bytes", "gsr_ehm_forward",
+           "gsr_deform_gaussians_backward", "gsr_backward_batch_deformed",
            # include/gsr_ssim.h
            "gsr_fused_ssim", "gsr_fused_ssim_backward", "gsr_image_loss_partials", "gsr_image_loss")
 
@@ -70,6 +71,12 @@ class DeformInputs(ctypes.Structure):
                 ("vtx_scale_stride", _i64), ("binding_face", _vp), ("face_bary", _vp), ("local_xyz", _vp),
                 ("local_stride", _i64), ("uv_rotations", _vp), ("uv_rot_stride", _i64), ("uv_scales", _vp),
                 ("uv_scale_stride", _i64), ("bad_index_flag", _vp)]
+
+
+class DeformGrads(ctypes.Structure):
+    """GsrDeformGrads (include/gsr_deform.h): the canonical attributes' gradients; None = not wanted."""
+    _fields_ = [("vtx_rotations", _vp), ("vtx_scales", _vp), ("local_xyz", _vp), ("uv_rotations", _vp),
+                ("uv_scales", _vp)]
 
 
 class RowSegment(ctypes.Structure):
@@ -243,6 +250,13 @@ def load(path=None):
     L.gsr_deform_gaussians.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
                                        _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
     L.gsr_deform_gaussians.restype = _i
+    L.gsr_deform_gaussians_backward.argtypes = [_i, ctypes.POINTER(DeformInputs), _vp, _vp, _vp,
+                                                ctypes.POINTER(DeformGrads), _vp]
+    L.gsr_deform_gaussians_backward.restype = _i
+    L.gsr_backward_batch_deformed.argtypes = [_i, _i, _i, ctypes.POINTER(DeformInputs), _vp, _vp, _vp, _vp, _i64,
+                                              _vp, _i64, _f, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                              _vp, ctypes.POINTER(DeformGrads), _i, _u32, _vp]
+    L.gsr_backward_batch_deformed.restype = _i
     L.gsr_ehm_workspace_bytes.argtypes = [ctypes.POINTER(Ehm), _i]
     L.gsr_ehm_workspace_bytes.restype = _sz
     L.gsr_ehm_forward.argtypes = [ctypes.POINTER(Ehm), _i, ctypes.POINTER(EhmParam), ctypes.POINTER(EhmOutputs),

@@ -291,6 +291,65 @@ class BatchRasterizer:
         del keep
         return g
 
+    def backward_deformed(self, deformer, verts, vert_transforms, deformed, colors, opacities, viewmatrices,
+                          projmatrices, tanfov, backgrounds, dL_dcolor, dL_dinvdepth=None, scale_modifier=1.0,
+                          antialiasing=False, numerics=None):
+        """Gradients of the last forward() of a posed avatar with respect to its CANONICAL attributes
+        (include/gsr_deform.h gsr_backward_batch_deformed): `deformer` (deform.GaussianDeformer) holds
+        the shared canonical attributes, `deformed` is the dict its forward(verts, vert_transforms)
+        returned and forward() rendered from ('xyz', 'rotation', 'scaling' [B,P,k]); colors [P,32] and
+        opacities [P,1] are shared by the frames.  Returns a dict of the seven gradients summed over
+        the frames: vtx_rotations [V,4], vtx_scales [V,3], local_pos [N,3], uv_rotations [N,4],
+        uv_scales [N,3], colors [P,32], opacity [P,1].  The per-frame [B,P,k] attribute gradients are
+        never written.  verts / vert_transforms get no gradient."""
+        B, P, dfm = self.B, self.P, deformer
+        if getattr(self, "_fwd_only", False):
+            raise _lib.GsrError("backward after a forward-only forward: the workspace holds no backward rows")
+        if dfm.V + dfm.N != P:
+            raise ValueError(f"deformer has {dfm.V + dfm.N} Gaussians, the rasterizer {P}")
+        if tuple(verts.shape) != (B, dfm.V, 3) or tuple(vert_transforms.shape) != (B, dfm.V, 4, 4):
+            raise ValueError("verts / vert_transforms: expected [B,V,3] / [B,V,4,4]")
+        for name, t_ in (("verts", verts), ("vert_transforms", vert_transforms), ("deformer.faces", dfm.faces)):
+            if t_.device != self.device:
+                raise ValueError(f"{name} is on {t_.device}, the rasterizer on {self.device}")
+        nm = self.numerics if numerics is None else int(numerics)
+        o = dict(dtype=torch.float32, device=self.device)
+        keep, head, (v, pm, tf, bg, bs) = self._inputs(deformed["xyz"], colors, opacities, deformed["scaling"],
+                                                       deformed["rotation"], viewmatrices, projmatrices, tanfov,
+                                                       backgrounds)
+        full = (3 * P, 0, 0, 3 * P, 4 * P)  # means3D, colors, opacities, scales, rotations frame strides
+        if tuple(head[5::2]) != full:
+            raise ValueError("backward_deformed needs deformed attributes [B,P,k] and colors / opacities shared "
+                             "by every frame ([P,k] tensors or frame stride 0)")
+        if tuple(dL_dcolor.shape) != (B, C, self.H, self.W):
+            raise ValueError(f"dL_dcolor: expected [{B},{C},{self.H},{self.W}], got {list(dL_dcolor.shape)}")
+        dLc = dL_dcolor.to(torch.float32).contiguous()
+        dLi = None
+        if dL_dinvdepth is not None:
+            if dL_dinvdepth.numel() != B * self.H * self.W:
+                raise ValueError("dL_dinvdepth: expected [B,H,W]")
+            dLi = dL_dinvdepth.to(torch.float32).contiguous()
+        vb = verts.detach().to(torch.float32).contiguous()
+        vt = vert_transforms.detach().to(torch.float32).contiguous()
+        di = _lib.DeformInputs(dfm.V, dfm.faces.shape[0], dfm.N, 0, vb.data_ptr(), vt.data_ptr(),
+                               dfm.faces.data_ptr(), dfm.v_rot.data_ptr(), 0, dfm.v_scale.data_ptr(), 0,
+                               dfm.bind.data_ptr(), dfm.bary.data_ptr(), dfm.u_local.data_ptr(), 0,
+                               dfm.u_rot.data_ptr(), 0, dfm.u_scale.data_ptr(), 0, dfm.bad.data_ptr())
+        g = dict(vtx_rotations=torch.zeros((dfm.V, 4), **o), vtx_scales=torch.zeros((dfm.V, 3), **o),
+                 local_pos=torch.zeros((dfm.N, 3), **o), uv_rotations=torch.zeros((dfm.N, 4), **o),
+                 uv_scales=torch.zeros((dfm.N, 3), **o), colors=torch.zeros((P, C), **o),
+                 opacity=torch.zeros((P, 1), **o))
+        dgr = _lib.DeformGrads(g["vtx_rotations"].data_ptr(), g["vtx_scales"].data_ptr(), g["local_pos"].data_ptr(),
+                               g["uv_rotations"].data_ptr(), g["uv_scales"].data_ptr())
+        rc = self.L.gsr_backward_batch_deformed(
+            B, self.W, self.H, ctypes.byref(di), head[4], head[12], head[10], head[6], 0, head[8], 0,
+            float(scale_modifier), v, pm, tf, bg, bs, self.workspace.data_ptr(), self.R_capacity, dLc.data_ptr(),
+            dLi.data_ptr() if dLi is not None else None, g["opacity"].data_ptr(), g["colors"].data_ptr(),
+            ctypes.byref(dgr), int(bool(antialiasing)), nm, self._stream())
+        _lib.check(rc, "gsr_backward_batch_deformed")
+        del keep, vb, vt
+        return g
+
     def status(self):
         """(R_total, overflow) of the last forward; synchronises the stream."""
         R = ctypes.c_int64(0)

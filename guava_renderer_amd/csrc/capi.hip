@@ -195,6 +195,11 @@ size_t carve_bin(char* base, int64_t R, BinArena* b, bool qmask) {
 // the fused assembly + projection of the avatar pipeline (deform.hip)
 void launch_deform_preprocess(const Dims& d, const Inputs& in, const GeomArena& g, const Outputs& o,
                               const GsrDeformInputs& dg, hipStream_t s);
+// the projection backward of a posed avatar, written as canonical gradients (preprocess_bwd.hip)
+void launch_preprocess_bwd_deformed(const Dims& d, const Inputs& in, const GeomArena& g, const Grads& gr,
+                                    const GsrDeformInputs& dg, const GsrDeformGrads& dgr, hipStream_t s);
+// the host-side checks of a GsrDeformInputs (deform.hip): 0, or api_fail(GSR_ERR_ARG, who: ...)
+int check_deform_inputs(int B, const GsrDeformInputs* dg, const char* who);
 
 }  // namespace gsr
 
@@ -713,7 +718,7 @@ static int backward_batch(int B, int P, int width, int height, const float* mean
                           float scale_modifier, const float* viewmatrices, const float* projmatrices,
                           const float* tanfov, const float* backgrounds, int64_t bg_stride, char* workspace,
                           int64_t R_capacity, const Grads& grads, int antialiasing, uint32_t numerics,
-                          hipStream_t s) {
+                          hipStream_t s, const GsrDeformInputs* dg = nullptr, const GsrDeformGrads* dgr = nullptr) {
     if (B <= 0 || P <= 0 || !workspace || !tanfov) return fail(GSR_ERR_ARG, "bad batch arguments");
     if (numerics & ~kNumericsKnown) return fail(GSR_ERR_ARG, "unknown numerics flags");
     if (P >= kMaxGaussians) return fail(GSR_ERR_ARG, "P must be < 2^24");
@@ -737,7 +742,13 @@ static int backward_batch(int B, int P, int width, int height, const float* mean
     in.scale_mod = scale_modifier;
     in.antialiasing = antialiasing;
     { StageTimer st_(7, s); launch_render_bwd(d, in, g, im, bn, grads, exact_exp(numerics), split_bf16(numerics), s); }
-    { StageTimer st_(8, s); launch_preprocess_bwd(d, in, g, grads, s); }
+    if (dg) {  // a posed avatar: the projection backward writes the canonical attributes' gradients
+        StageTimer st_(8, s);
+        launch_preprocess_bwd_deformed(d, in, g, grads, *dg, *dgr, s);
+    } else {
+        StageTimer st_(8, s);
+        launch_preprocess_bwd(d, in, g, grads, s);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GSR_ERR_HIP, std::string("backward_batch: ") + hipGetErrorString(e));
     return 0;
@@ -802,6 +813,41 @@ int gsr_backward_batch_shared(int B, int P, int width, int height, const float* 
                           opac_stride, scales, scales_stride, rotations, rot_stride, scale_modifier,
                           viewmatrices, projmatrices, tanfov, backgrounds, bg_stride, workspace, R_capacity, gr,
                           antialiasing, numerics, (hipStream_t)stream);
+}
+
+int gsr_backward_batch_deformed(int B, int width, int height, const GsrDeformInputs* dg, const float* means3D,
+                                const float* rotations, const float* scales, const float* colors,
+                                int64_t colors_stride, const float* opacities, int64_t opac_stride,
+                                float scale_modifier, const float* viewmatrices, const float* projmatrices,
+                                const float* tanfov, const float* backgrounds, int64_t bg_stride,
+                                char* workspace, int64_t R_capacity, const float* dL_dpix,
+                                const float* dL_dinvdepth, float* dL_dopacity, float* dL_dcolor,
+                                const GsrDeformGrads* grads, int antialiasing, uint32_t numerics,
+                                void* stream) {
+    if (const int rc = check_deform_inputs(B, dg, "gsr_backward_batch_deformed")) return rc;
+    if (dg->V + dg->N == 0) return fail(GSR_ERR_ARG, "gsr_backward_batch_deformed: no Gaussians");
+    if (dg->vtx_rot_stride || dg->vtx_scale_stride || dg->local_stride || dg->uv_rot_stride ||
+        dg->uv_scale_stride || colors_stride || opac_stride)
+        return fail(GSR_ERR_ARG, "gsr_backward_batch_deformed: canonical attributes, colors and opacities must be "
+                                 "shared by every frame (stride 0)");
+    if (!means3D || !rotations || !scales || !colors || !opacities)
+        return fail(GSR_ERR_ARG, "gsr_backward_batch_deformed: needs the deformed attributes, colors and opacities");
+    if (!dL_dpix || !dL_dopacity || !dL_dcolor || !grads)
+        return fail(GSR_ERR_ARG, "gsr_backward_batch_deformed: null gradient buffer");
+    if ((dg->V > 0 && (!grads->vtx_rotations || !grads->vtx_scales)) ||
+        (dg->N > 0 && (!grads->local_xyz || !grads->uv_rotations || !grads->uv_scales)))
+        return fail(GSR_ERR_ARG, "gsr_backward_batch_deformed: null canonical gradient buffer");
+    const int P = dg->V + dg->N;
+    Grads gr{};
+    gr.dL_dpix = dL_dpix;
+    gr.dL_dinvdepth = dL_dinvdepth;
+    gr.invd = dL_dinvdepth != nullptr;
+    gr.reduce = 1;
+    gr.dL_dopacity = dL_dopacity;
+    gr.dL_dcolors = dL_dcolor;
+    return backward_batch(B, P, width, height, means3D, 3LL * P, colors, 0, opacities, 0, scales, 3LL * P, rotations,
+                          4LL * P, scale_modifier, viewmatrices, projmatrices, tanfov, backgrounds, bg_stride,
+                          workspace, R_capacity, gr, antialiasing, numerics, (hipStream_t)stream, dg, grads);
 }
 
 int gsr_render_counters(uint64_t* device_counters) {

@@ -28,6 +28,8 @@
 //   k_lbs_skin       V x B            T_v = sum_j w_vj A_j, v = T_v [v_posed; 1]
 //   k_deform_gaussians (V+N) x B/8    vertex + UV Gaussians straight into the rasterizer's inputs
 //                                     (face frames once per face and frame, in LDS)
+//   k_deform_gaussians_bwd (V+N) x 1  gradients of the canonical attributes (shared ones: frame sums in
+//                                     frame order in one thread; per-frame only: (V+N) x B/8); no LDS
 // Every sum runs in a fixed order (fmaf chains over k in index order, 3-term dots left to right),
 // so results are deterministic run to run.
 #include <climits>
@@ -36,6 +38,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_deform.h"
+#include "deform_dev.h"
 #include "deform_internal.h"
 #include "gsr_internal.h"
 #include "preprocess_dev.h"
@@ -1085,66 +1088,7 @@ __global__ __launch_bounds__(256) void k_splice_head(
     }
 }
 
-// roma.rotmat_to_unitquat (scipy's from_matrix decision scheme), row-major m -> (x, y, z, w).
-// The branch on the largest of (m00, m11, m22, trace) picks one of four candidate quaternions;
-// the candidates share their off-diagonal sums, so all four are formed with 7 adds and the choice
-// is made with selects (no dynamically indexed arrays, which compile to compare/select ladders).
-__device__ __forceinline__ float4 rotmat_to_unitquat(const float m[9]) {
-    const float d0 = m[0], d1 = m[4], d2 = m[8];
-    const float d3 = (d0 + d1) + d2;
-    int ch = 0;
-    float best = d0;
-    if (d1 > best) { best = d1; ch = 1; }
-    if (d2 > best) { best = d2; ch = 2; }
-    if (d3 > best) { best = d3; ch = 3; }
-    const float t = 1.0f - d3;
-    const float s01 = m[1] + m[3], s02 = m[2] + m[6], s12 = m[5] + m[7];  // m[3j+i] + m[3i+j]
-    const float r0 = m[7] - m[5], r1 = m[2] - m[6], r2 = m[3] - m[1];     // the w candidates
-    float4 q;
-    q.x = ch == 0 ? t + 2.0f * m[0] : ch == 1 ? s01 : ch == 2 ? s02 : r0;
-    q.y = ch == 0 ? s01 : ch == 1 ? t + 2.0f * m[4] : ch == 2 ? s12 : r1;
-    q.z = ch == 0 ? s02 : ch == 1 ? s12 : ch == 2 ? t + 2.0f * m[8] : r2;
-    q.w = ch == 0 ? r0 : ch == 1 ? r1 : ch == 2 ? r2 : 1.0f + d3;
-    const float n = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-    return make_float4(q.x / n, q.y / n, q.z / n, q.w / n);
-}
-
-// roma.quat_product, xyzw: (p_w q_v + q_w p_v + p_v x q_v, p_w q_w - p_v . q_v)
-__device__ __forceinline__ float4 quat_product(float4 p, float4 q) {
-    float4 o;
-    o.x = (p.w * q.x + q.w * p.x) + (p.y * q.z - p.z * q.y);
-    o.y = (p.w * q.y + q.w * p.y) + (p.z * q.x - p.x * q.z);
-    o.z = (p.w * q.z + q.w * p.z) + (p.x * q.y - p.y * q.x);
-    o.w = p.w * q.w - ((p.x * q.x + p.y * q.y) + p.z * q.z);
-    return o;
-}
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
-
-// compute_face_orientation (graphics_utils.py:61-80, safe_normalize eps 1e-20) of one deformed face
-// and the frame's rotmat_to_unitquat (ubody_gaussian.py:257-258): fr = {m[9] (row-major, columns
-// a0 a1 a2), s, q.xyzw}.
-__device__ __forceinline__ void face_frame(const float* __restrict__ vb, int i0, int i1, int i2, float fr[14]) {
-    const float v0x = vb[3 * i0], v0y = vb[3 * i0 + 1], v0z = vb[3 * i0 + 2];
-    const float e1x = vb[3 * i1] - v0x, e1y = vb[3 * i1 + 1] - v0y, e1z = vb[3 * i1 + 2] - v0z;
-    const float e2x = vb[3 * i2] - v0x, e2y = vb[3 * i2 + 1] - v0y, e2z = vb[3 * i2 + 2] - v0z;
-    const float l1 = sqrtf(fmaxf(dot3(e1x, e1y, e1z, e1x, e1y, e1z), 1e-20f));
-    const float a0x = e1x / l1, a0y = e1y / l1, a0z = e1z / l1;
-    const float c1x = a0y * e2z - a0z * e2y, c1y = a0z * e2x - a0x * e2z, c1z = a0x * e2y - a0y * e2x;
-    const float lc1 = sqrtf(fmaxf(dot3(c1x, c1y, c1z, c1x, c1y, c1z), 1e-20f));
-    const float a1x = c1x / lc1, a1y = c1y / lc1, a1z = c1z / lc1;
-    const float c2x = a1y * a0z - a1z * a0y, c2y = a1z * a0x - a1x * a0z, c2z = a1x * a0y - a1y * a0x;
-    const float lc2 = sqrtf(fmaxf(dot3(c2x, c2y, c2z, c2x, c2y, c2z), 1e-20f));
-    const float a2x = -(c2x / lc2), a2y = -(c2y / lc2), a2z = -(c2z / lc2);
-    const float m[9] = {a0x, a1x, a2x, a0y, a1y, a2y, a0z, a1z, a2z};
-    const float4 q = rotmat_to_unitquat(m);
-#pragma unroll
-    for (int k = 0; k < 9; k++) fr[k] = m[k];
-    fr[9] = (l1 + fabsf(dot3(a2x, a2y, a2z, e2x, e2y, e2z))) / 2.0f;
-    fr[10] = q.x; fr[11] = q.y; fr[12] = q.z; fr[13] = q.w;
-}
+// (rotmat_to_unitquat, quat_product, dot3 and face_frame: deform_dev.h)
 
 constexpr int kDeformFrames = 8;  // frames per workgroup (GSR_DEFORM_FRAMES overrides, timing only)
 constexpr int kFrStride = 15;  // LDS floats per face frame (odd: conflict-free per-thread rows)
@@ -1374,6 +1318,112 @@ void launch_deform_preprocess(const Dims& d, const Inputs& in, const GeomArena& 
                        g, o);
 }
 
+// Backward of k_deform_gaussians with respect to the canonical attributes (deform_dev.h): one thread
+// per Gaussian walks frames [blockIdx.y * fpw, ...) in frame order.  An attribute shared by every
+// frame (stride 0) gets its frame sum, accumulated in registers and written once (the launch then has
+// grid.y = 1, as k_preprocess_bwd's reduce mode); a per-frame attribute gets one row per frame.  No
+// atomics, no scatter, so the sums are deterministic.  Face frames are recomputed per thread (the
+// forward's face_frame): the kernel has no LDS and no barrier.  A Gaussian with an out-of-range
+// binding gets zero rows and sets the flag; nothing is read out of range.  verts and
+// vert_transforms get no gradient (include/gsr_deform.h).
+__global__ __launch_bounds__(256) void k_deform_gaussians_bwd(int B, int fpw, GsrDeformInputs dg,
+                                                              const float* __restrict__ g_means,
+                                                              const float* __restrict__ g_rots,
+                                                              const float* __restrict__ g_scales, GsrDeformGrads o) {
+    const int V = dg.V, N = dg.N, P = V + N;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const int b0 = blockIdx.y * fpw, b1 = min(B, b0 + fpw);
+    if (i < V) {
+        float ar[4] = {0.f, 0.f, 0.f, 0.f}, as[3] = {0.f, 0.f, 0.f};
+        for (int b = b0; b < b1; b++) {
+            const int64_t gid = (int64_t)b * P + i;
+            if (o.vtx_rotations) {
+                const float* qv = dg.vtx_rotations + b * dg.vtx_rot_stride + 4 * (int64_t)i;
+                const float q[4] = {qv[0], qv[1], qv[2], qv[3]};
+                const float g[4] = {g_rots[4 * gid], g_rots[4 * gid + 1], g_rots[4 * gid + 2], g_rots[4 * gid + 3]};
+                float dq[4];
+                deform_bwd_vertex_rot(dg.vert_transforms + ((int64_t)b * V + i) * 16, q, g, dq);
+                if (dg.vtx_rot_stride) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) o.vtx_rotations[b * dg.vtx_rot_stride + 4 * (int64_t)i + k] = dq[k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) ar[k] += dq[k];
+                }
+            }
+            if (o.vtx_scales) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const float gs = g_scales[3 * gid + k];
+                    if (dg.vtx_scale_stride) o.vtx_scales[b * dg.vtx_scale_stride + 3 * (int64_t)i + k] = gs;
+                    else as[k] += gs;
+                }
+            }
+        }
+        if (o.vtx_rotations && !dg.vtx_rot_stride)
+#pragma unroll
+            for (int k = 0; k < 4; k++) o.vtx_rotations[4 * (int64_t)i + k] = ar[k];
+        if (o.vtx_scales && !dg.vtx_scale_stride)
+#pragma unroll
+            for (int k = 0; k < 3; k++) o.vtx_scales[3 * (int64_t)i + k] = as[k];
+        return;
+    }
+    const int n = i - V;
+    const DeformBinding bd = resolve_binding(dg.binding_face, dg.faces, n, V, dg.F);
+    if (bd.f < 0 && dg.bad_index_flag && blockIdx.y == 0) atomicOr(dg.bad_index_flag, 1u);
+    float al[3] = {0.f, 0.f, 0.f}, ar[4] = {0.f, 0.f, 0.f, 0.f}, as[3] = {0.f, 0.f, 0.f};
+    for (int b = b0; b < b1; b++) {
+        const int64_t gid = (int64_t)b * P + i;
+        float dl[3] = {0.f, 0.f, 0.f}, dr[4] = {0.f, 0.f, 0.f, 0.f}, ds[3] = {0.f, 0.f, 0.f};
+        if (bd.f >= 0) {
+            float fr[14];
+            face_frame_bwd(dg.verts + (int64_t)b * V * 3, bd.j0, bd.j1, bd.j2, fr);
+            float gm[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f};
+            if (o.local_xyz)
+#pragma unroll
+                for (int k = 0; k < 3; k++) gm[k] = g_means[3 * gid + k];
+            if (o.uv_rotations)
+#pragma unroll
+                for (int k = 0; k < 4; k++) gq[k] = g_rots[4 * gid + k];
+            if (o.uv_scales)
+#pragma unroll
+                for (int k = 0; k < 3; k++) gs[k] = g_scales[3 * gid + k];
+            deform_bwd_uv(fr, gm, gq, gs, dl, dr, ds);
+        }
+        if (o.local_xyz) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                if (dg.local_stride) o.local_xyz[b * dg.local_stride + 3 * (int64_t)n + k] = dl[k];
+                else al[k] += dl[k];
+            }
+        }
+        if (o.uv_rotations) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (dg.uv_rot_stride) o.uv_rotations[b * dg.uv_rot_stride + 4 * (int64_t)n + k] = dr[k];
+                else ar[k] += dr[k];
+            }
+        }
+        if (o.uv_scales) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                if (dg.uv_scale_stride) o.uv_scales[b * dg.uv_scale_stride + 3 * (int64_t)n + k] = ds[k];
+                else as[k] += ds[k];
+            }
+        }
+    }
+    if (o.local_xyz && !dg.local_stride)
+#pragma unroll
+        for (int k = 0; k < 3; k++) o.local_xyz[3 * (int64_t)n + k] = al[k];
+    if (o.uv_rotations && !dg.uv_rot_stride)
+#pragma unroll
+        for (int k = 0; k < 4; k++) o.uv_rotations[4 * (int64_t)n + k] = ar[k];
+    if (o.uv_scales && !dg.uv_scale_stride)
+#pragma unroll
+        for (int k = 0; k < 3; k++) o.uv_scales[3 * (int64_t)n + k] = as[k];
+}
+
 struct PackTable {
     GsrRowSegment seg[GSR_PACK_MAX_SEGMENTS];
 };
@@ -1426,6 +1476,27 @@ int hip_check(const char* what) {
 }
 
 }  // namespace
+
+// gsr_deform_gaussians' host-side checks on a GsrDeformInputs (also gsr_backward_batch_deformed's)
+int check_deform_inputs(int B, const GsrDeformInputs* dg, const char* who) {
+    auto bad = [&](const char* msg) { return api_fail(GSR_ERR_ARG, (std::string(who) + ": " + msg).c_str()); };
+    if (!dg) return bad("null deform inputs");
+    if (B <= 0 || dg->V < 0 || dg->N < 0 || dg->F < 0) return bad("bad sizes");
+    if (dg->V + dg->N == 0) return 0;
+    if (!dg->verts) return bad("null required pointer");
+    if (dg->V > 0 && (!dg->vert_transforms || !dg->vtx_rotations || !dg->vtx_scales))
+        return bad("vertex Gaussians need transforms, rotations, scales");
+    if (dg->N > 0 && (!dg->faces || !dg->binding_face || !dg->face_bary || !dg->local_xyz || !dg->uv_rotations ||
+                      !dg->uv_scales || dg->F == 0))
+        return bad("UV Gaussians need faces and binding data");
+    auto bad_stride = [](int64_t st, int64_t full) { return st != 0 && st != full; };
+    if (bad_stride(dg->vtx_rot_stride, 4LL * dg->V) || bad_stride(dg->vtx_scale_stride, 3LL * dg->V) ||
+        bad_stride(dg->local_stride, 3LL * dg->N) || bad_stride(dg->uv_rot_stride, 4LL * dg->N) ||
+        bad_stride(dg->uv_scale_stride, 3LL * dg->N))
+        return bad("strides must be 0 or a whole frame");
+    return 0;
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -1980,6 +2051,32 @@ int gsr_deform_gaussians(int B, int V, int F, int N, const float* verts,
                        uv_rot_stride, uv_scales, uv_scale_stride, means3D, rotations, scales,
                        bad_index_flag);
     return hip_check("deform_gaussians");
+}
+
+int gsr_deform_gaussians_backward(int B, const GsrDeformInputs* dg, const float* dL_dmeans3D,
+                                  const float* dL_drotations, const float* dL_dscales,
+                                  const GsrDeformGrads* grads, void* stream) {
+    const char* who = "gsr_deform_gaussians_backward";
+    if (const int rc = check_deform_inputs(B, dg, who)) return rc;
+    if (!grads) return api_fail(GSR_ERR_ARG, "gsr_deform_gaussians_backward: null gradient struct");
+    const int P = dg->V + dg->N;
+    if (P == 0) return 0;
+    GsrDeformGrads o = *grads;
+    if (dg->V == 0) o.vtx_rotations = o.vtx_scales = nullptr;
+    if (dg->N == 0) o.local_xyz = o.uv_rotations = o.uv_scales = nullptr;
+    if (!o.vtx_rotations && !o.vtx_scales && !o.local_xyz && !o.uv_rotations && !o.uv_scales) return 0;
+    if (((o.vtx_rotations || o.uv_rotations) && !dL_drotations) || ((o.vtx_scales || o.uv_scales) && !dL_dscales) ||
+        (o.local_xyz && !dL_dmeans3D))
+        return api_fail(GSR_ERR_ARG, "gsr_deform_gaussians_backward: a wanted gradient needs its upstream gradient");
+    // a wanted output shared by every frame is a sum over all B frames in one thread (grid.y = 1);
+    // with per-frame outputs only, the frames are grouped per workgroup as in the forward
+    const bool any_shared = (o.vtx_rotations && !dg->vtx_rot_stride) || (o.vtx_scales && !dg->vtx_scale_stride) ||
+                            (o.local_xyz && !dg->local_stride) || (o.uv_rotations && !dg->uv_rot_stride) ||
+                            (o.uv_scales && !dg->uv_scale_stride);
+    const int fpw = any_shared || B < kDeformFrames ? B : kDeformFrames;
+    hipLaunchKernelGGL(k_deform_gaussians_bwd, dim3((P + 255) / 256, (B + fpw - 1) / fpw), dim3(256), 0,
+                       (hipStream_t)stream, B, fpw, *dg, dL_dmeans3D, dL_drotations, dL_dscales, o);
+    return hip_check("deform_gaussians_backward");
 }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
 // preprocess_bwd.hip -- per-Gaussian backward of the projection: computeCov2DCUDA
 // (backward.cu:147-326), preprocessCUDA bwd (:398-449) and computeCov3D bwd (:330-393) of the
 // reference, fused into one launch (the reference uses two).
+// k_preprocess_bwd_deformed: the same for a posed avatar, continued through the Gaussian assembly's
+// backward into the canonical attributes' gradients (gsr_backward_batch_deformed).
+#include "deform_dev.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -9,10 +12,11 @@ __device__ __forceinline__ float sqf(float x) { return x * x; }
 
 // Gradients of Gaussian i in frame b; returns false (outputs untouched) when it was culled there.
 // The per-frame outputs (mean2D, conic, cov3D, invdepth) are stored unless gr.reduce; the
-// attributes' gradients come back in o_mean / o_op / o_scale / o_rot.
+// attributes' gradients come back in o_mean / o_op / o_scale / o_rot (the last two when geo: the
+// caller wants them and the forward had scales and rotations).
 __device__ __forceinline__ bool preprocess_bwd_frame(const Dims& d, const Inputs& in, const GeomArena& g,
-                                                     const Grads& gr, int b, int i, float o_mean[3], float& o_op,
-                                                     float o_scale[3], float o_rot[4]) {
+                                                     const Grads& gr, int b, int i, bool geo, float o_mean[3],
+                                                     float& o_op, float o_scale[3], float o_rot[4]) {
     const int64_t gid = (int64_t)b * d.P + i;
     if (!(g.radii[gid] > 0)) return false;
     const float* view = in.view + 16 * b;
@@ -149,7 +153,7 @@ __device__ __forceinline__ bool preprocess_bwd_frame(const Dims& d, const Inputs
     o_mean[2] = dm[2];
 
     // ---- computeCov3D bwd ----
-    if (in.scales && in.rot && gr.dL_dscale && gr.dL_drot) {
+    if (geo) {
         const float* q = in.rot + in.s_rot * b + 4 * (int64_t)i;
         const float r = q[0], x = q[1], y = q[2], z = q[3];
         const mat3 R = mk3(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(kScanBlock) void k_preprocess_bwd(Dims d, Inputs in
         const int b = blockIdx.y;
         const int64_t gid = (int64_t)b * d.P + i;
         float m[3], sc[3], r[4], op;
-        if (!preprocess_bwd_frame(d, in, g, gr, b, i, m, op, sc, r)) return;
+        if (!preprocess_bwd_frame(d, in, g, gr, b, i, geo, m, op, sc, r)) return;
         gr.dL_dopacity[gid] = op;
 #pragma unroll
         for (int k = 0; k < 3; k++) gr.dL_dmeans3D[3 * gid + k] = m[k];
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(kScanBlock) void k_preprocess_bwd(Dims d, Inputs in
     float am[3] = {0.f, 0.f, 0.f}, as[3] = {0.f, 0.f, 0.f}, ar[4] = {0.f, 0.f, 0.f, 0.f}, aop = 0.f;
     for (int b = 0; b < d.B; b++) {
         float m[3], sc[3] = {0.f, 0.f, 0.f}, r[4] = {0.f, 0.f, 0.f, 0.f}, op;
-        if (!preprocess_bwd_frame(d, in, g, gr, b, i, m, op, sc, r)) continue;
+        if (!preprocess_bwd_frame(d, in, g, gr, b, i, geo, m, op, sc, r)) continue;
         aop += op;
 #pragma unroll
         for (int k = 0; k < 3; k++) { am[k] += m[k]; as[k] += sc[k]; }
@@ -228,6 +232,72 @@ __global__ __launch_bounds__(kScanBlock) void k_preprocess_bwd(Dims d, Inputs in
 #pragma unroll
         for (int k = 0; k < 4; k++) gr.dL_drot[4 * (int64_t)i + k] = ar[k];
     }
+}
+
+// k_preprocess_bwd's frame-reduced mode for a posed avatar (gsr_backward_batch_deformed): in.means3D /
+// scales / rot are the deformed [B,P,k] attributes of gsr_deform_gaussians, and each frame's
+// (mean, scale, rotation) gradient goes from registers through the assembly's backward
+// (deform_dev.h) into the canonical attributes' sums, written once.  One thread per Gaussian, frames
+// in order; no LDS, no barrier.  The vertex Gaussians' mean gradient has no canonical attribute to go
+// to (include/gsr_deform.h).  A Gaussian culled in a frame adds nothing for it; one with an
+// out-of-range binding was NaN in the forward, so culled in every frame: zero rows, flag set.
+__global__ __launch_bounds__(kScanBlock) void k_preprocess_bwd_deformed(Dims d, Inputs in, GeomArena g, Grads gr,
+                                                                        GsrDeformInputs dg, GsrDeformGrads o) {
+    const int i = blockIdx.x * kScanBlock + threadIdx.x;
+    if (i >= d.P || g.ctrl[kCtrlFwdOnly]) return;
+    const int V = dg.V;
+    const bool vtx = i < V;
+    const int n = i - V;
+    DeformBinding bd{-1, 0, 0, 0};
+    if (!vtx) {
+        bd = resolve_binding(dg.binding_face, dg.faces, n, V, dg.F);
+        if (bd.f < 0 && dg.bad_index_flag) atomicOr(dg.bad_index_flag, 1u);
+    }
+    float qv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (vtx)
+#pragma unroll
+        for (int k = 0; k < 4; k++) qv[k] = dg.vtx_rotations[4 * (int64_t)i + k];
+    float al[3] = {0.f, 0.f, 0.f}, as[3] = {0.f, 0.f, 0.f}, ar[4] = {0.f, 0.f, 0.f, 0.f}, aop = 0.f;
+    for (int b = 0; b < d.B; b++) {
+        float m[3], sc[3] = {0.f, 0.f, 0.f}, r[4] = {0.f, 0.f, 0.f, 0.f}, op;
+        if (!vtx && bd.f < 0) continue;
+        if (!preprocess_bwd_frame(d, in, g, gr, b, i, true, m, op, sc, r)) continue;
+        aop += op;
+        if (vtx) {
+            float dq[4];
+            deform_bwd_vertex_rot(dg.vert_transforms + ((int64_t)b * V + i) * 16, qv, r, dq);
+#pragma unroll
+            for (int k = 0; k < 4; k++) ar[k] += dq[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) as[k] += sc[k];
+        } else {
+            float fr[14], dl[3], dq[4], ds[3];
+            face_frame_bwd(dg.verts + (int64_t)b * V * 3, bd.j0, bd.j1, bd.j2, fr);
+            deform_bwd_uv(fr, m, r, sc, dl, dq, ds);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { al[k] += dl[k]; as[k] += ds[k]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) ar[k] += dq[k];
+        }
+    }
+    gr.dL_dopacity[i] = aop;
+    if (vtx) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) o.vtx_rotations[4 * (int64_t)i + k] = ar[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) o.vtx_scales[3 * (int64_t)i + k] = as[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o.local_xyz[3 * (int64_t)n + k] = al[k]; o.uv_scales[3 * (int64_t)n + k] = as[k]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) o.uv_rotations[4 * (int64_t)n + k] = ar[k];
+    }
+}
+
+void launch_preprocess_bwd_deformed(const Dims& d, const Inputs& in, const GeomArena& g, const Grads& gr,
+                                    const GsrDeformInputs& dg, const GsrDeformGrads& dgr, hipStream_t s) {
+    if (d.P == 0 || d.B == 0) return;
+    hipLaunchKernelGGL(k_preprocess_bwd_deformed, dim3(d.nblk), dim3(kScanBlock), 0, s, d, in, g, gr, dg, dgr);
 }
 
 void launch_preprocess_bwd(const Dims& d, const Inputs& in, const GeomArena& g, const Grads& gr,

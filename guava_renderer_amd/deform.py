@@ -249,6 +249,102 @@ class GaussianDeformer:
         return bool(self.bad.item())
 
 
+def _attr(t, B, n, k, name):
+    """(float32 contiguous tensor, frame stride) of a canonical attribute [n,k] (shared, stride 0) or
+    [B,n,k] (per frame)."""
+    if tuple(t.shape) == (n, k):
+        return _f32(t), 0
+    if tuple(t.shape) == (B, n, k):
+        return _f32(t), n * k
+    raise ValueError(f"{name}: expected [{n},{k}] or [{B},{n},{k}], got {list(t.shape)}")
+
+
+def deform_inputs(B, verts, vert_transforms, faces, binding_face, face_bary, attrs, bad):
+    """The _lib.DeformInputs block of one assembly call and the tensors it points to (keep them alive
+    until the launch is enqueued).  attrs: (vtx_rotations, vtx_scales, local_pos, uv_rotations,
+    uv_scales), each [n,k] or [B,n,k]."""
+    V, N = verts.shape[1], binding_face.shape[0]
+    (vr, s_vr), (vs, s_vs), (ul, s_ul), (ur, s_ur), (us, s_us) = (
+        _attr(t, B, n, k, name) for t, n, k, name in zip(
+            attrs, (V, V, N, N, N), (4, 3, 3, 4, 3),
+            ("vtx_rotations", "vtx_scales", "local_pos", "uv_rotations", "uv_scales")))
+    keep = (verts, vert_transforms, faces, binding_face, face_bary, vr, vs, ul, ur, us, bad)
+    _dev_check(*keep)
+    di = _lib.DeformInputs(V, faces.shape[0], N, 0, _ptr(verts), _ptr(vert_transforms), _ptr(faces), _ptr(vr), s_vr,
+                           _ptr(vs), s_vs, _ptr(binding_face), _ptr(face_bary), _ptr(ul), s_ul, _ptr(ur), s_ur,
+                           _ptr(us), s_us, _ptr(bad))
+    return di, keep
+
+
+class _DeformGaussians(torch.autograd.Function):
+    """gsr_deform_gaussians with gsr_deform_gaussians_backward as its backward (include/gsr_deform.h)."""
+
+    @staticmethod
+    def forward(ctx, verts, vert_transforms, faces, binding_face, face_bary, bad, *attrs):
+        B, V = verts.shape[:2]
+        N = binding_face.shape[0]
+        P = V + N
+        di, keep = deform_inputs(B, verts, vert_transforms, faces, binding_face, face_bary, attrs, bad)
+        # GaussianDeformer.forward's allocation: the rotations first (the kernel stores them as float4)
+        buf = torch.empty((B * P * 10,), dtype=torch.float32, device=verts.device)
+        rot = buf[:B * P * 4].view(B, P, 4)
+        xyz = buf[B * P * 4:B * P * 7].view(B, P, 3)
+        scl = buf[B * P * 7:].view(B, P, 3)
+        rc = _lib.load().gsr_deform_gaussians(
+            B, V, di.F, N, di.verts, di.vert_transforms, di.faces, di.vtx_rotations, di.vtx_rot_stride,
+            di.vtx_scales, di.vtx_scale_stride, di.binding_face, di.face_bary, di.local_xyz, di.local_stride,
+            di.uv_rotations, di.uv_rot_stride, di.uv_scales, di.uv_scale_stride, _ptr(xyz), _ptr(rot), _ptr(scl),
+            di.bad_index_flag, _stream(verts.device))
+        _lib.check(rc, "gsr_deform_gaussians")
+        ctx.save_for_backward(*keep[:10])
+        ctx.bad = bad
+        ctx.attr_shapes = [tuple(a.shape) for a in attrs]
+        return xyz, rot, scl
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_rot, g_scl):
+        verts, vt, faces, bind, bary = ctx.saved_tensors[:5]
+        attrs = ctx.saved_tensors[5:]
+        B, dev = verts.shape[0], verts.device
+        di, keep = deform_inputs(B, verts, vt, faces, bind, bary, attrs, ctx.bad)
+        need = ctx.needs_input_grad[6:]
+        outs = [torch.zeros(shp, dtype=torch.float32, device=dev) if nd else None
+                for shp, nd in zip(ctx.attr_shapes, need)]
+        dgr = _lib.DeformGrads(*[None if o is None else o.data_ptr() for o in outs])
+        P = verts.shape[1] + bind.shape[0]
+        # (an output the loss does not use has no gradient: zeros)
+        ups = [torch.zeros((B, P, k), dtype=torch.float32, device=dev) if g is None else _f32(g)
+               for g, k in zip((g_xyz, g_rot, g_scl), (3, 4, 3))]
+        rc = _lib.load().gsr_deform_gaussians_backward(B, ctypes.byref(di), _ptr(ups[0]), _ptr(ups[1]),
+                                                       _ptr(ups[2]), ctypes.byref(dgr), _stream(dev))
+        _lib.check(rc, "gsr_deform_gaussians_backward")
+        del keep
+        return (None,) * 6 + tuple(outs)
+
+
+def deform_gaussians(verts, vert_transforms, faces, binding_face, face_bary, vtx_rotations, vtx_scales,
+                     local_pos, uv_rotations, uv_scales, bad_index_flag=None):
+    """Differentiable Gaussian assembly (ubody_gaussian.py:252-278): (xyz [B,P,3], rotation [B,P,4],
+    scaling [B,P,3]), bit-identical to GaussianDeformer.forward, with gradients for the five canonical
+    attribute tensors, each [n,k] (shared by the frames; its gradient is the frame sum) or [B,n,k].
+    verts [B,V,3] and vert_transforms [B,V,4,4] get NO gradient (include/gsr_deform.h: the face frames
+    and the vertex transforms' quaternions are constants of this backward), so one that requires grad
+    is refused instead of silently training with a missing term.  bad_index_flag: int32 [1] device
+    tensor ORed with 1 on an out-of-range binding (default: a fresh one, not returned)."""
+    if verts.requires_grad or vert_transforms.requires_grad:
+        raise NotImplementedError("deform_gaussians has no gradient for verts / vert_transforms "
+                                  "(detach them: the mesh is a constant of the canonical attributes' backward)")
+    _dev_check(verts, vert_transforms)
+    if verts.dim() != 3 or tuple(vert_transforms.shape) != tuple(verts.shape[:2]) + (4, 4):
+        raise ValueError("verts / vert_transforms: expected [B,V,3] / [B,V,4,4]")
+    faces = faces.detach().to(torch.int32).contiguous()
+    bind = binding_face.detach().reshape(-1).to(torch.int32).contiguous()
+    bary = _f32(face_bary.reshape(-1, 3))
+    bad = bad_index_flag if bad_index_flag is not None else torch.zeros(1, dtype=torch.int32, device=verts.device)
+    return _DeformGaussians.apply(_f32(verts), _f32(vert_transforms), faces, bind, bary, bad, vtx_rotations,
+                                  vtx_scales, local_pos, uv_rotations, uv_scales)
+
+
 def _host(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
 

@@ -21,6 +21,10 @@
  *                           normalize) and UV Gaussians (compute_face_orientation,
  *                           utils/graphics_utils.py:61-80, face binding, barycentric centre,
  *                           face-scaled local offset and scale), concatenated vertex-first.
+ *   gsr_deform_gaussians_backward, gsr_backward_batch_deformed
+ *                        <- torch autograd through the same lines with respect to the canonical
+ *                           attributes (what main/trainer.py's backward does for them), standalone
+ *                           and fused into the rasterizer's projection backward.
  *
  * Conventions: device pointers, float32, the reference's layouts unless stated.  Two operands are
  * taken k-major (transposed once at avatar load, so the per-frame kernels read them coalesced):
@@ -270,6 +274,62 @@ int gsr_deform_gaussians(int B, int V, int F, int N, const float* verts,
                          const float* uv_rotations, int64_t uv_rot_stride,
                          const float* uv_scales, int64_t uv_scale_stride, float* means3D,
                          float* rotations, float* scales, uint32_t* bad_index_flag, void* stream);
+
+/* Gradients of the assembly with respect to the CANONICAL attributes, the ones GUAVA trains: vertex
+ * rotations and scales, UV local offsets, rotations and scales.  A NULL member means "not wanted".
+ * Each output has its input's mode: [n,k], summed over the B frames in frame order, where the
+ * input's stride is 0; [B,n,k], one row per frame, where it is a whole frame. */
+typedef struct {
+    float* vtx_rotations;  /* [V,4] or [B,V,4] wxyz */
+    float* vtx_scales;     /* [V,3] or [B,V,3] */
+    float* local_xyz;      /* [N,3] or [B,N,3] */
+    float* uv_rotations;   /* [N,4] or [B,N,4] wxyz */
+    float* uv_scales;      /* [N,3] or [B,N,3] */
+} GsrDeformGrads;
+
+/* Backward of gsr_deform_gaussians: dg = the forward's inputs; dL_dmeans3D [B,P,3], dL_drotations
+ * [B,P,4] (wxyz), dL_dscales [B,P,3] = the gradients of its outputs (P = V + N, vertex Gaussians
+ * first; one may be NULL when no wanted output needs it).  With (x) roma's xyzw quat_product:
+ *   vertex rotation  out = r / max(|r|, 1e-12), r = q(T_v) (x) q_v:
+ *                    g_r = (g - out (out . g)) / max(|r|, 1e-12), dL/dq_v = conj(q(T_v)) (x) g_r
+ *   vertex scale     dL/dscale_v = g_scale
+ *   UV rotation      out = q_f (x) q_uv (not normalised): dL/dq_uv = conj(q_f) (x) g
+ *   UV offset        dL/dlocal = s M^T g_xyz;   UV scale: dL/dscale_uv = s g_scale
+ * with M, s, q_f the face frame, scale and quaternion of the deformed binding face (the forward's own
+ * function).  Along this path the face frame and the vertex transform's quaternion are CONSTANTS:
+ * nothing differentiates through rotmat_to_unitquat, compute_face_orientation or the LBS.
+ * verts and vert_transforms get NO gradient, deliberately: tracking and EHM fitting are out of scope,
+ * and that path needs the backward of the branchy quaternion scheme and a scatter over shared
+ * vertices.  So the vertex Gaussians' dL_dmeans3D and the UV centres' dependence on the mesh are
+ * dropped.  Every frame sum runs in frame order inside one thread (no atomics): deterministic.
+ * A Gaussian with an out-of-range binding gets zero gradient rows and ORs 1 into
+ * dg->bad_index_flag; nothing is read out of range. */
+int gsr_deform_gaussians_backward(int B, const GsrDeformInputs* dg, const float* dL_dmeans3D,
+                                  const float* dL_drotations, const float* dL_dscales,
+                                  const GsrDeformGrads* grads, void* stream);
+
+/* The rasterizer backward of a posed avatar with SHARED canonical attributes, colours and opacities
+ * under B poses and B cameras, after gsr_deform_gaussians + gsr_forward_batch on `workspace`:
+ * gsr_backward_batch's two launches (render backward, projection backward), the second writing the
+ * canonical gradients (the arithmetic of gsr_deform_gaussians_backward, per frame from registers,
+ * summed over the frames in frame order) -- the [B,P,10] attribute gradients never reach HBM.
+ *   dg: the assembly's inputs; every canonical stride must be 0, as colors_stride and opac_stride
+ *   (GSR_ERR_ARG otherwise).  means3D [B,P,3], rotations [B,P,4], scales [B,P,3]: the deformed
+ *   attributes the forward rendered from.  colors [P,32], opacities [P,1].
+ *   dL_dpix [B,32,H,W], dL_dinvdepth [B,H,W] or NULL.
+ * Outputs: dL_dopacity [P,1], dL_dcolor [P,32] (ACCUMULATED: zero it first), grads (every member
+ * required for the Gaussian kind that exists).  A Gaussian culled in a frame contributes nothing for
+ * that frame.  A GSR_FORWARD_ONLY workspace (gsr_forward_batch_deformed's included) is refused, an
+ * overflowed forward gives the gradients gsr_backward_batch_shared gives. */
+int gsr_backward_batch_deformed(int B, int width, int height, const GsrDeformInputs* dg, const float* means3D,
+                                const float* rotations, const float* scales, const float* colors,
+                                int64_t colors_stride, const float* opacities, int64_t opac_stride,
+                                float scale_modifier, const float* viewmatrices, const float* projmatrices,
+                                const float* tanfov, const float* backgrounds, int64_t bg_stride,
+                                char* workspace, int64_t R_capacity, const float* dL_dpix,
+                                const float* dL_dinvdepth, float* dL_dopacity, float* dL_dcolor,
+                                const GsrDeformGrads* grads, int antialiasing, uint32_t numerics,
+                                void* stream);
 
 #ifdef __cplusplus
 }
