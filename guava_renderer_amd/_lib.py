@@ -16,6 +16,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_backward_batch", "gsr_backward_batch_shared", "gsr_batch_status", "gsr_profile_enable", "gsr_profile_read",
            "gsr_render_counters", "gsr_render_timeline", "gsr_forward_batch_refine",
            "gsr_refine_prepare", "gsr_batch_status_offset", "gsr_frames_to8b",
+           "gsr_refine_backward_scratch_bytes", "gsr_refine_backward_image", "gsr_refine_backward_rows",
            "gsr_stream_create_cu_mask", "gsr_stream_destroy", "gsr_set_render_stream",
            # include/gsr_deform.h
            "gsr_lbs_workspace_bytes", "gsr_lbs", "gsr_lbs_sp", "gsr_blend_joints", "gsr_blend_joints_sp",
@@ -56,6 +57,13 @@ class RefineEpilogue(ctypes.Structure):
     """gsr_refine_epilogue (include/gsr.h)."""
     _fields_ = [("weight", _vp), ("bias", _vp), ("n_out", _i), ("negative_slope", _f),
                 ("out_refine", _vp), ("keep_channels", _i)]
+
+
+class RefineBackwardDesc(ctypes.Structure):
+    """gsr_refine_backward_desc (include/gsr.h)."""
+    _fields_ = [("weight", _vp), ("n_out", _i), ("keep_channels", _i), ("negative_slope", _f), ("pad_", _i),
+                ("out_refine", _vp), ("dL_dout_refine", _vp), ("dL_dkeep", _vp), ("dL_dprepared", _vp),
+                ("scratch", _vp)]
 
 
 class Scratch(ctypes.Structure):
@@ -200,6 +208,13 @@ def load(path=None):
     L.gsr_forward_batch_deformed.restype = _i
     L.gsr_refine_prepare.argtypes = [_i, _vp, _vp, _i, _i, _vp, _vp]
     L.gsr_refine_prepare.restype = _i
+    L.gsr_refine_backward_scratch_bytes.argtypes = [_i, _i, _i, _i, _i]
+    L.gsr_refine_backward_scratch_bytes.restype = _sz
+    L.gsr_refine_backward_image.argtypes = [_i, _i, _i, _i, _vp, _i64, ctypes.POINTER(RefineBackwardDesc), _vp]
+    L.gsr_refine_backward_image.restype = _i
+    L.gsr_refine_backward_rows.argtypes = [_i, _i, _vp, _vp, _i64, _i, _vp, _vp, _i64,
+                                           ctypes.POINTER(RefineBackwardDesc), _vp, _vp, _vp, _vp]
+    L.gsr_refine_backward_rows.restype = _i
     L.gsr_backward_batch.argtypes = [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                      _i64, _f, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u32, _vp]

@@ -88,6 +88,7 @@ class BatchRasterizer:
         self._overflow = self.workspace[4:8].view(torch.int32).reshape(())  # this call's flag (kCtrlOverflow)
         self._status_host = torch.zeros(4, dtype=torch.int32, pin_memory=True)
         self._status_ev = None
+        self._fwd_count = 0  # forwards enqueued on the (single-use) workspace
         self.out_color = torch.empty((self.B, C, self.H, self.W), dtype=torch.float32, device=self.device)
         self.out_invdepth = torch.empty((self.B, self.H, self.W), dtype=torch.float32, device=self.device)
         self.radii = torch.empty((self.B, self.P), dtype=torch.int32, device=self.device)
@@ -125,6 +126,7 @@ class BatchRasterizer:
 
     def _after_forward(self):
         """Queue the asynchronous copy of the sticky status words (no host synchronisation)."""
+        self._fwd_count += 1
         self._status_host.copy_(self._sticky, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
@@ -291,9 +293,118 @@ class BatchRasterizer:
         del keep
         return g
 
+    def _bg_arg(self, backgrounds):
+        """(rows [B,32] or [1,32], element stride between frames) of a [32] or [B,32] background."""
+        if backgrounds.device != self.device or backgrounds.dtype != torch.float32:
+            raise ValueError(f"backgrounds must be float32 on {self.device}")
+        if tuple(backgrounds.shape) == (C,):
+            return backgrounds.contiguous().reshape(1, C), 0
+        if backgrounds.dim() != 2 or tuple(backgrounds.shape) != (self.B, C):
+            raise ValueError(f"backgrounds: expected [{C}] or [{self.B},{C}], got {list(backgrounds.shape)}")
+        if backgrounds.stride(0) == 0:
+            return backgrounds[0].contiguous().reshape(1, C), 0
+        return backgrounds.contiguous(), C
+
+    def refine_backward_image(self, head, dL_drefined, dL_draw=None, out_refine=None):
+        """The image end of the refine backward (include/gsr.h gsr_refine_backward_image): from
+        dL/d(refined) [B,n_out,H,W] and optionally dL/d(kept raw channels) [B,keep,H,W] the gradient
+        image in prepared channel space [B,32,H,W], the dL_dcolor of a backward() on head.prepare'd
+        rows.  out_refine: the forward's refined output (default head.out, the last forward's).
+        Returns (image, scratch); scratch goes to refine_backward_rows."""
+        B, P, H, W = self.B, self.P, self.H, self.W
+        if getattr(self, "_fwd_only", False):
+            raise _lib.GsrError("backward after a forward-only forward: the workspace holds no backward rows")
+        out = head.out if out_refine is None else out_refine
+        if out is None or tuple(out.shape) != (B, head.n_out, H, W):
+            raise ValueError(f"out_refine: expected the refine forward's [{B},{head.n_out},{H},{W}] output")
+        if tuple(dL_drefined.shape) != (B, head.n_out, H, W):
+            raise ValueError(f"dL_drefined: expected [{B},{head.n_out},{H},{W}], got {list(dL_drefined.shape)}")
+        if out.device != self.device or dL_drefined.device != self.device:
+            raise ValueError(f"out_refine / dL_drefined must be on {self.device}")
+        out = out.to(torch.float32).contiguous()
+        dout = dL_drefined.to(torch.float32).contiguous()
+        dkeep = None
+        if dL_draw is not None and head.keep_channels > 0:
+            if tuple(dL_draw.shape) != (B, head.keep_channels, H, W) or dL_draw.device != self.device:
+                raise ValueError(f"dL_draw: expected [{B},{head.keep_channels},{H},{W}] on {self.device}")
+            dkeep = dL_draw.to(torch.float32).contiguous()
+        # one scratch for both ends, whichever row layout (frame-reduced or per frame) follows
+        nbytes = max(self.L.gsr_refine_backward_scratch_bytes(B, W, H, P, 1),
+                     self.L.gsr_refine_backward_scratch_bytes(B, W, H, B * P, B))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        G = torch.empty((B, C, H, W), dtype=torch.float32, device=self.device)
+        desc = _lib.RefineBackwardDesc(head.weight.data_ptr(), head.n_out, head.keep_channels, head.slope, 0,
+                                       out.data_ptr(), dout.data_ptr(),
+                                       dkeep.data_ptr() if dkeep is not None else None, G.data_ptr(),
+                                       scratch.data_ptr())
+        _lib.check(self.L.gsr_refine_backward_image(B, P, W, H, self.workspace.data_ptr(), self.R_capacity,
+                                                    ctypes.byref(desc), self._stream()),
+                   "gsr_refine_backward_image")
+        del out, dout, dkeep
+        return G, scratch
+
+    def refine_backward_rows(self, head, d_prepared, raw_rows, backgrounds, scratch):
+        """The row end of the refine backward (gsr_refine_backward_rows): d_prepared is the colour
+        gradient of the backward on the prepared rows ([P,32] frame-reduced or [B,P,32]), raw_rows the
+        raw features ([P,32] or [B,P,32]), backgrounds the raw ones.  Returns (gradient of the raw
+        rows, shaped as d_prepared; weight gradient [n_out,32]; bias gradient [n_out])."""
+        B, P, dev = self.B, self.P, self.device
+        raw, rs = _frame_arg(raw_rows, B, P, C, "raw_rows", dev, align16=True)
+        if d_prepared.dtype != torch.float32 or d_prepared.device != dev or \
+                tuple(d_prepared.shape) not in ((P, C), (B, P, C)):
+            raise ValueError(f"d_prepared: expected float32 [{P},{C}] or [{B},{P},{C}] on {dev}")
+        frames = 1 if d_prepared.dim() == 2 else B
+        if frames == 1 and rs != 0:
+            raise ValueError("frame-reduced d_prepared [P,32] needs raw rows shared by every frame")
+        dp = d_prepared.contiguous()
+        bg, bs = self._bg_arg(backgrounds)
+        need = self.L.gsr_refine_backward_scratch_bytes(B, self.W, self.H, dp.numel() // C, frames)
+        if scratch.numel() < need:
+            raise ValueError("scratch is not the one refine_backward_image returned for this rasterizer")
+        o = dict(dtype=torch.float32, device=dev)
+        rows = torch.empty_like(dp)
+        dW = torch.empty((head.n_out, C), **o)
+        db = torch.empty((head.n_out,), **o)
+        desc = _lib.RefineBackwardDesc(head.weight.data_ptr(), head.n_out, head.keep_channels, head.slope, 0,
+                                       None, None, None, None, scratch.data_ptr())
+        _lib.check(self.L.gsr_refine_backward_rows(dp.numel() // C, frames, dp.data_ptr(), raw.data_ptr(), rs, B,
+                                                   scratch.data_ptr(), bg.data_ptr(), bs, ctypes.byref(desc),
+                                                   rows.data_ptr(), dW.data_ptr(), db.data_ptr(), self._stream()),
+                   "gsr_refine_backward_rows")
+        del raw, bg, dp
+        return rows, dW, db
+
+    def _prepared(self, head, colors, backgrounds):
+        """(prepared colours, prepared backgrounds as backward() takes them) -- head.prepare's cached
+        rows when `colors` is the tensor the forward prepared."""
+        raw, _ = _frame_arg(colors, self.B, self.P, C, "colors", self.device, align16=True)
+        bg, bs = self._bg_arg(backgrounds)
+        pc = head.prepare(raw, self._stream())
+        pb = head.prepare(bg, self._stream(), cache=False)
+        return pc, (pb if bs else pb[0])
+
+    def backward_refine(self, head, means3D, colors, opacities, scales, rotations, viewmatrices, projmatrices,
+                        tanfov, backgrounds, dL_drefined, dL_draw=None, dL_dinvdepth=None, scale_modifier=1.0,
+                        antialiasing=False, shared=False, numerics=None, out_refine=None):
+        """Gradients of the last forward(..., refine=head): the arguments of backward() with the image
+        gradient split into dL_drefined [B,n_out,H,W] (of head.out) and the optional dL_draw
+        [B,keep,H,W] (of out_color[:, :keep]).  Returns backward()'s dict with `colors` the gradient of
+        the RAW features, plus `weight` [n_out,32] and `bias` [n_out] of the head.  The 32-channel
+        feature image is never formed: the image gradient is mapped into the prepared channel space
+        (refine_backward_image), the ordinary backward runs on the prepared rows, and
+        refine_backward_rows maps its colour gradient back and contracts the weight gradient."""
+        G, scratch = self.refine_backward_image(head, dL_drefined, dL_draw, out_refine)
+        pc, pb = self._prepared(head, colors, backgrounds)
+        g = self.backward(means3D, pc, opacities, scales, rotations, viewmatrices, projmatrices, tanfov, pb, G,
+                          dL_dinvdepth, scale_modifier=scale_modifier, antialiasing=antialiasing, shared=shared,
+                          numerics=numerics)
+        g["colors"], g["weight"], g["bias"] = self.refine_backward_rows(head, g["colors"], colors, backgrounds,
+                                                                        scratch)
+        return g
+
     def backward_deformed(self, deformer, verts, vert_transforms, deformed, colors, opacities, viewmatrices,
-                          projmatrices, tanfov, backgrounds, dL_dcolor, dL_dinvdepth=None, scale_modifier=1.0,
-                          antialiasing=False, numerics=None):
+                          projmatrices, tanfov, backgrounds, dL_dcolor=None, dL_dinvdepth=None, scale_modifier=1.0,
+                          antialiasing=False, numerics=None, refine=None, dL_drefined=None, dL_draw=None):
         """Gradients of the last forward() of a posed avatar with respect to its CANONICAL attributes
         (include/gsr_deform.h gsr_backward_batch_deformed): `deformer` (deform.GaussianDeformer) holds
         the shared canonical attributes, `deformed` is the dict its forward(verts, vert_transforms)
@@ -301,7 +412,23 @@ class BatchRasterizer:
         opacities [P,1] are shared by the frames.  Returns a dict of the seven gradients summed over
         the frames: vtx_rotations [V,4], vtx_scales [V,3], local_pos [N,3], uv_rotations [N,4],
         uv_scales [N,3], colors [P,32], opacity [P,1].  The per-frame [B,P,k] attribute gradients are
-        never written.  verts / vert_transforms get no gradient."""
+        never written.  verts / vert_transforms get no gradient.
+        refine=head, dL_drefined= (and optionally dL_draw=) instead of dL_dcolor: the forward was
+        forward(..., refine=head); as backward_refine, `colors` comes back as the gradient of the raw
+        features and `weight`, `bias` of the head are added."""
+        if refine is not None:
+            if dL_drefined is None or dL_dcolor is not None:
+                raise ValueError("backward_deformed(refine=head) takes dL_drefined (and dL_draw), not dL_dcolor")
+            G, scratch = self.refine_backward_image(refine, dL_drefined, dL_draw)
+            pc, pb = self._prepared(refine, colors, backgrounds)
+            g = self.backward_deformed(deformer, verts, vert_transforms, deformed, pc, opacities, viewmatrices,
+                                       projmatrices, tanfov, pb, G, dL_dinvdepth, scale_modifier=scale_modifier,
+                                       antialiasing=antialiasing, numerics=numerics)
+            g["colors"], g["weight"], g["bias"] = self.refine_backward_rows(refine, g["colors"], colors, backgrounds,
+                                                                            scratch)
+            return g
+        if dL_dcolor is None:
+            raise ValueError("backward_deformed needs dL_dcolor (or refine= and dL_drefined=)")
         B, P, dfm = self.B, self.P, deformer
         if getattr(self, "_fwd_only", False):
             raise _lib.GsrError("backward after a forward-only forward: the workspace holds no backward rows")
@@ -420,6 +547,65 @@ class RefineHead:
         return _lib.RefineEpilogue(self.weight.data_ptr(),
                                    self.bias.data_ptr() if self.bias is not None else None,
                                    self.n_out, self.slope, out.data_ptr(), self.keep_channels)
+
+
+class _RenderRefined(torch.autograd.Function):
+    """forward(refine=head) + backward_refine as one autograd node (render_refined)."""
+
+    @staticmethod
+    def forward(ctx, rast, opts, weight, bias, means3D, colors, opacities, scales, rotations, viewmatrices,
+                projmatrices, tanfov, backgrounds):
+        slope, keep, scale_modifier, antialiasing, numerics = opts
+        # a head per call: its output buffer is this call's own, so `refined` survives later forwards
+        head = RefineHead(weight, bias, slope, keep)
+        attrs = tuple(t.detach() for t in (means3D, colors, opacities, scales, rotations))
+        cams = tuple(t.detach() for t in (viewmatrices, projmatrices, tanfov, backgrounds))
+        col, inv, radii = rast.forward(*attrs, *cams, scale_modifier=scale_modifier, antialiasing=antialiasing,
+                                       refine=head, numerics=numerics)
+        raw, invd, rad = col[:, :keep].clone(), inv.clone(), radii.clone()
+        ctx.rast, ctx.head, ctx.opts, ctx.attrs, ctx.cams = rast, head, opts, attrs, cams
+        ctx.count = rast._fwd_count
+        ctx.shapes = (weight.shape, tuple(t.dim() for t in attrs))
+        ctx.mark_non_differentiable(rad)
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not zeros
+        return raw, head.out, invd, rad
+
+    @staticmethod
+    def backward(ctx, d_raw, d_refined, d_invdepth, _d_radii):
+        rast, head = ctx.rast, ctx.head
+        if rast._fwd_count != ctx.count:
+            raise _lib.GsrError("render_refined: another forward ran on this rasterizer before backward(); the "
+                                "workspace holds that forward's state, not this one's")
+        _, _, scale_modifier, antialiasing, numerics = ctx.opts
+        wshape, dims = ctx.shapes
+        if d_refined is None:
+            d_refined = torch.zeros_like(head.out)
+        shared = all(d == 2 for d in dims)
+        g = rast.backward_refine(head, *ctx.attrs, *ctx.cams, d_refined, dL_draw=d_raw, dL_dinvdepth=d_invdepth,
+                                 scale_modifier=scale_modifier, antialiasing=antialiasing, shared=shared,
+                                 numerics=numerics, out_refine=head.out)
+        per = [g["means3D"], g["colors"], g["opacity"], g["scales"], g["rotations"]]
+        if not shared:  # an attribute shared by the frames gets the sum of its per-frame gradients
+            per = [t.sum(0) if d == 2 else t for t, d in zip(per, dims)]
+        need = ctx.needs_input_grad
+        grads = [None, None, g["weight"].reshape(wshape), g["bias"] if head.bias is not None else None] + per + \
+                [None, None, None, None]
+        return tuple(gr if nd else None for gr, nd in zip(grads, need))
+
+
+def render_refined(rast, weight, bias, means3D, colors, opacities, scales, rotations, viewmatrices, projmatrices,
+                   tanfov, backgrounds, negative_slope=0.2, keep_channels=4, scale_modifier=1.0, antialiasing=False,
+                   numerics=None):
+    """Differentiable render + fused refiner head (conv_body_first + leaky ReLU) on `rast`
+    (a BatchRasterizer): returns (raw [B,keep,H,W], refined [B,n_out,H,W], invdepth [B,H,W], radii
+    [B,P]) -- tensors of this call's own, so the rest of a StyleUNet chains onto `refined` in ordinary
+    torch.  .backward() fills the gradients of weight [n_out,32(,1,1)], bias [n_out] (or None) and of
+    the five attributes; attributes all given as [P,k] take the frame-reduced backward.  The
+    workspace is single-use: a backward after another forward on `rast` raises GsrError.  viewmatrices,
+    projmatrices, tanfov and backgrounds get no gradient."""
+    opts = (float(negative_slope), int(keep_channels), float(scale_modifier), bool(antialiasing), numerics)
+    return _RenderRefined.apply(rast, opts, weight, bias, means3D, colors, opacities, scales, rotations,
+                                viewmatrices, projmatrices, tanfov, backgrounds)
 
 
 def profile_enable(stages=("render_fwd",)):

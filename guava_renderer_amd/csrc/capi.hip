@@ -850,6 +850,85 @@ int gsr_backward_batch_deformed(int B, int width, int height, const GsrDeformInp
                           workspace, R_capacity, gr, antialiasing, numerics, (hipStream_t)stream, dg, grads);
 }
 
+// ---- backward of the refiner head (refine_bwd.hip) ----
+// scratch: the frame sums [B][64], then one region used first by the image end's partial rows and
+// then by the row end's partial tiles
+static size_t refine_sums_bytes(int B) { return align_up((size_t)B * 64 * sizeof(float)); }
+
+static const char* refine_desc_error(const gsr_refine_backward_desc* desc) {
+    if (!desc) return "null desc";
+    if (!desc->weight || !desc->scratch) return "null weight or scratch";
+    if (desc->n_out < 1) return "n_out must be >= 1";
+    if (desc->keep_channels < 0 || desc->keep_channels + desc->n_out > GSR_C) return "keep_channels + n_out must be <= 32";
+    if (!(desc->negative_slope >= 0.0f))
+        return "negative_slope must be >= 0 (the sign is taken from the forward's output)";
+    return nullptr;
+}
+
+size_t gsr_refine_backward_scratch_bytes(int B, int width, int height, int n, int row_frames) {
+    if (B <= 0 || width <= 0 || height <= 0 || n < 0 || row_frames <= 0) return 0;
+    const size_t img = (size_t)B * refine_image_workgroups(width, height) * 64;
+    const int rpf = n / row_frames;
+    const int rpw = refine_rows_per_workgroup(rpf);
+    const size_t rows = (size_t)row_frames * ((rpf + rpw - 1) / rpw) * GSR_C * GSR_C;
+    return refine_sums_bytes(B) + align_up((img > rows ? img : rows) * sizeof(float));
+}
+
+int gsr_refine_backward_image(int B, int P, int width, int height, char* workspace, int64_t R_capacity,
+                              const gsr_refine_backward_desc* desc, void* stream) {
+    if (const char* e = refine_desc_error(desc))
+        return fail(GSR_ERR_ARG, std::string("gsr_refine_backward_image: ") + e);
+    if (B <= 0 || P <= 0 || width <= 0 || height <= 0 || !workspace)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: bad batch arguments");
+    if (B > kMaxFrames) return fail(GSR_ERR_ARG, "gsr_refine_backward_image: too many frames per batch");
+    if ((int64_t)((width + 15) / 16) * ((height + 15) / 16) > kMaxTiles)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: image too large");
+    if (!desc->out_refine || !desc->dL_dout_refine || !desc->dL_dprepared)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: null out_refine, dL_dout_refine or dL_dprepared");
+    if (workspace_fwd_only(workspace))
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: the workspace's last forward was GSR_FORWARD_ONLY "
+                                 "(no final_T)");
+    const Dims d = make_dims(B, P, width, height);
+    GeomArena g;
+    ImageArena im;
+    BinArena bn;
+    carve_workspace(workspace, d, R_capacity, &g, &im, &bn);
+    float* sums = desc->scratch;
+    float* partials = reinterpret_cast<float*>(reinterpret_cast<char*>(desc->scratch) + refine_sums_bytes(B));
+    launch_refine_bwd_image(B, width, height, g.ctrl, im.final_T, desc->out_refine, desc->dL_dout_refine,
+                            desc->dL_dkeep, desc->n_out, desc->keep_channels, desc->negative_slope,
+                            desc->dL_dprepared, partials, sums, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, std::string("refine_backward_image: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int gsr_refine_backward_rows(int n, int row_frames, const float* d_prepared, const float* raw_rows,
+                             int64_t raw_stride, int B, const float* frame_sums, const float* raw_backgrounds,
+                             int64_t bg_stride, const gsr_refine_backward_desc* desc, float* dL_drows,
+                             float* dL_dweight, float* dL_dbias, void* stream) {
+    if (const char* e = refine_desc_error(desc))
+        return fail(GSR_ERR_ARG, std::string("gsr_refine_backward_rows: ") + e);
+    if (n < 0 || row_frames < 1 || row_frames > kMaxFrames || n % row_frames != 0 ||
+        n / row_frames >= kMaxGaussians || B <= 0 || B > kMaxFrames)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_rows: n must be row_frames frames of < 2^24 rows, "
+                                 "1 <= B, row_frames <= 256");
+    if (!frame_sums || !raw_backgrounds || !dL_dweight)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_rows: null frame_sums, raw_backgrounds or dL_dweight");
+    if (n > 0 && (!d_prepared || !raw_rows || !dL_drows))
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_rows: null d_prepared, raw_rows or dL_drows");
+    if ((((uintptr_t)d_prepared | (uintptr_t)raw_rows | (uintptr_t)dL_drows) & 15) != 0 || ((raw_stride * 4) & 15) != 0)
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_rows: rows must be 16-byte aligned per frame");
+    if (raw_stride < 0 || bg_stride < 0) return fail(GSR_ERR_ARG, "gsr_refine_backward_rows: negative stride");
+    float* tiles = reinterpret_cast<float*>(reinterpret_cast<char*>(desc->scratch) + refine_sums_bytes(B));
+    launch_refine_bwd_rows(n, row_frames, d_prepared, raw_rows, raw_stride, desc->weight, desc->n_out,
+                           desc->keep_channels, B, frame_sums, raw_backgrounds, bg_stride, tiles, dL_drows,
+                           dL_dweight, dL_dbias, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, std::string("refine_backward_rows: ") + hipGetErrorString(e));
+    return 0;
+}
+
 int gsr_render_counters(uint64_t* device_counters) {
     g_render_counters = device_counters;
     return 0;

@@ -344,6 +344,20 @@ void launch_preprocess_bwd(const Dims& d, const Inputs& in, const GeomArena& g, 
                            hipStream_t s);
 void launch_refine_prepare(int n, const float* in, const float* w, int n_out, int keep, float* out,
                            hipStream_t s);
+// backward of the refiner head (refine_bwd.hip).  Image end: G' [B][32][H][W] and the per-frame sums
+// frame_sums [B][64] (dbias part 32, S = sum_px final_T dz 32) through `partials`
+// (B x refine_image_workgroups x 64 floats).  Row end: drows [n][32], dW [n_out][32], dbias [n_out]
+// (or null) through `tiles` (row_frames x workgroups per frame x 32 x 32 floats); the n rows are
+// row_frames frames of n / row_frames rows, frame f reading its raw rows at raw + f * raw_stride.
+constexpr int kRefinePixPerWg = 1024;
+int refine_image_workgroups(int W, int H);
+int refine_rows_per_workgroup(int rows_per_frame);
+void launch_refine_bwd_image(int B, int W, int H, const uint32_t* ctrl, const float* final_T, const float* out_refine,
+                             const float* dout, const float* dkeep, int n_out, int keep, float slope, float* G,
+                             float* partials, float* frame_sums, hipStream_t s);
+void launch_refine_bwd_rows(int n, int row_frames, const float* dprep, const float* raw, int64_t raw_stride,
+                            const float* W, int n_out, int keep, int B, const float* frame_sums, const float* bg,
+                            int64_t bg_stride, float* tiles, float* drows, float* dW, float* dbias, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, const float* proj,
                          uint8_t* present, hipStream_t s);
 

@@ -228,8 +228,9 @@ int gsr_backward_batch_shared(int B, int P, int width, int height, const float* 
  *                                            keeps 0-2 as raw_renders, 3 as extra_renders,
  *                                            gaussian_render.py:71,83); other channels unwritten
  *   out_refine[b][o]  = leaky_relu(channel keep+o + bias[o], negative_slope),  o < n_out
- * so the 33-channel feature image is never written nor re-read.  Forward-only (inference:
- * main/test.py, render_motion.py); keep_channels + n_out <= 32. */
+ * so the 33-channel feature image is never written nor re-read.  keep_channels + n_out <= 32.
+ * Inference (main/test.py, render_motion.py) adds GSR_FORWARD_ONLY; without it the forward keeps
+ * final_T and n_contrib and is differentiable through gsr_refine_backward_* below. */
 typedef struct {
     const float* weight;   /* [n_out][32] (Conv2d weight [n_out,32,1,1]); used by gsr_refine_prepare */
     const float* bias;     /* [n_out] or NULL */
@@ -250,6 +251,52 @@ int gsr_forward_batch_refine(int B, int P, int width, int height, const float* m
                              char* workspace, int64_t R_capacity, float* out_color, float* out_invdepth,
                              int* radii, int antialiasing, const gsr_refine_epilogue* refine,
                              uint32_t numerics, void* stream);
+/* Backward of the refine forward (training the head jointly with the Gaussians).  With M the 32x32
+ * map of gsr_refine_prepare (identity on channels [0, keep), `weight` on [keep, keep + n_out), zero
+ * below), the forward composites f' = M f over bg' = M bg, so its backward is the ordinary batch
+ * backward on the PREPARED rows between two ends:
+ *   1. gsr_refine_backward_image: from dL/dout_refine (and optionally dL/d of the kept raw channels)
+ *      the gradient image in prepared channel space, dL_dprepared [B][32][H][W]:
+ *        channel c < keep: dL_dkeep[c] (0 when NULL);  channel keep + o: dz[o] = dL_dout_refine[o] *
+ *        (out_refine[o] > 0 ? 1 : negative_slope) -- the sign of the forward's own output, 0 and -0
+ *        taking the slope as F.leaky_relu_'s in-place backward does (hence negative_slope >= 0);
+ *        every remaining channel 0.
+ *      It also leaves, at the head of `scratch`, the frame sums [B][64]: [b][o] = sum_px dz[o] and
+ *      [b][32 + o] = sum_px final_T dz[o] (the gradient of the prepared background).  After a
+ *      forward that overflowed the capacity all of it is zero (out_refine is NaN then).
+ *   2. gsr_backward_batch / _shared / _deformed with colors = the prepared rows, backgrounds = the
+ *      prepared backgrounds and dL_dpix = dL_dprepared.  Its geometry and opacity gradients are final;
+ *      its colour gradient is d' = dL/df' ([P,32] frame-reduced, or [B,P,32]).
+ *   3. gsr_refine_backward_rows: per row, dL_drows[c] = (c < keep ? d'[c] : 0) + sum_o W[o][c]
+ *      d'[keep + o];  dL_dweight[o][c] = sum_rows d'[row][keep + o] f[row][c] + sum_b S[b][o] bg[b][c];
+ *      dL_dbias[o] = sum_b,px dz[o].  The n rows are `row_frames` frames of n / row_frames rows (1:
+ *      frame-reduced d', B: per-frame d'), frame f reading its raw rows at raw_rows + f * raw_stride
+ *      (0 = rows shared by the frames).  The background gets no gradient.
+ * Every sum of 1 and 3 is deterministic (fixed-order partial sums, no atomics) and its order depends
+ * on the sizes only, not on the device.  `scratch`: gsr_refine_backward_scratch_bytes(B, width,
+ * height, n, row_frames) bytes of device memory, shared by the two calls of one backward. */
+typedef struct {
+    const float* weight;          /* [n_out][32] */
+    int n_out;                    /* >= 1 */
+    int keep_channels;            /* keep_channels + n_out <= 32 */
+    float negative_slope;         /* >= 0 */
+    int pad_;
+    const float* out_refine;      /* [B][n_out][H][W], the forward's output (image end only) */
+    const float* dL_dout_refine;  /* [B][n_out][H][W] (image end only) */
+    const float* dL_dkeep;        /* [B][keep_channels][H][W] or NULL = zeros (image end only) */
+    float* dL_dprepared;          /* [B][32][H][W], written (image end only) */
+    float* scratch;
+} gsr_refine_backward_desc;
+size_t gsr_refine_backward_scratch_bytes(int B, int width, int height, int n, int row_frames);
+int gsr_refine_backward_image(int B, int P, int width, int height, char* workspace, int64_t R_capacity,
+                              const gsr_refine_backward_desc* desc, void* stream);
+/* d_prepared, raw_rows and dL_drows are 16-byte aligned ([.., 32] rows; raw_stride a multiple of 4);
+ * frame_sums is the [B][64] block gsr_refine_backward_image left at desc->scratch; raw_backgrounds
+ * [B][32] with bg_stride (0 = one background); dL_dbias may be NULL. */
+int gsr_refine_backward_rows(int n, int row_frames, const float* d_prepared, const float* raw_rows,
+                             int64_t raw_stride, int B, const float* frame_sums, const float* raw_backgrounds,
+                             int64_t bg_stride, const gsr_refine_backward_desc* desc, float* dL_drows,
+                             float* dL_dweight, float* dL_dbias, void* stream);
 /* Stage timing with HIP events recorded on the launch stream around each stage whose bit is set in
  * `stage_mask` (bit i = stage i: 0 preprocess, 1 block scan, 2 depth sort, 3 chunk count,
  * 4 tile scan, 5 ordered scatter, 6 render fwd, 7 render bwd, 8 preprocess bwd); 0 disables.
