@@ -25,7 +25,8 @@
 //    sets a single frame's time.
 //
 // Roofline: per frame the kernel must read 156 B per visible Gaussian (features + 2D attributes)
-// and write 140 B per pixel (32 channels, inverse depth, final_T, n_contrib).
+// and write 140 B per pixel (32 channels, inverse depth, final_T, n_contrib); 132 B forward-only
+// (FWD: final_T and n_contrib are the backward's and are not written).
 #include "gsr_cull.h"
 #include "gsr_internal.h"
 
@@ -97,6 +98,21 @@ __device__ __forceinline__ float take_step(float alpha, float inv_depth, uint32_
     return w;
 }
 
+// Forward-only (FWD): no backward reads the pixel's last contributor, so the step carries neither the
+// list position nor `last` -- the same expressions in the same order for w, T, invd and done.
+__device__ __forceinline__ float take_step(float alpha, float inv_depth, float& T, float& invd, bool& done) {
+    const bool take = !done && !(alpha < 1.0f / 255.0f);
+    const float eff = take ? alpha : 0.0f;
+    const float test_T = T * (1.0f - eff);
+    const bool term = test_T < 0.0001f;
+    const bool contrib = take && !term;
+    const float w = contrib ? eff * T : 0.0f;
+    invd = fmaf(inv_depth, w, invd);
+    T = contrib ? test_T : T;
+    done = done || term;
+    return w;
+}
+
 // Split-bf16 accumulation (gsr_set_split_bf16): f = f_hi + f_lo with f_hi = bf16_rne(f),
 // f_lo = bf16_rne(f - f_hi); the four bf16 products f_hi.w_hi + f_lo.w_hi + f_hi.w_lo + f_lo.w_lo
 // are exact in f32, so the only loss is the split residual (|f - f_hi - f_lo| <= 2^-17 |f|, the same
@@ -133,7 +149,9 @@ __device__ __forceinline__ float4 rec_load(__amdgpu_buffer_rsrc_t rs, uint32_t o
 // channels [keep, keep + n_out) already hold the refiner head's 1x1 conv W.(C + T bg); they get the
 // bias and the leaky ReLU here and go to out_refine, channels [0, keep) to out_color, the rest
 // nowhere.  No extra registers: the blend loop is the same kernel.
-template <bool EMPTY, bool REFINE>
+// FWD (forward-only): final_T and n_contrib are the backward's state and are not stored; T is used
+// for C + T*bg only.
+template <bool EMPTY, bool REFINE, bool FWD = false>
 __device__ __forceinline__ void store_strip(const Dims& d, const ImageArena& im, const Outputs& o,
                                             const float* bg, int b, int sx0, int sy0, int lane,
                                             const floatx16& acc0, const floatx16& acc1, float T,
@@ -143,8 +161,10 @@ __device__ __forceinline__ void store_strip(const Dims& d, const ImageArena& im,
     const int py = sy0 + lane / kStripW;
     if (px < d.W && py < d.H) {
         const int64_t pix = b * HW + (int64_t)py * d.W + px;
-        im.final_T[pix] = T;
-        im.n_contrib[pix] = last;
+        if (!FWD) {
+            im.final_T[pix] = T;
+            im.n_contrib[pix] = last;
+        }
         if (o.out_invdepth) o.out_invdepth[pix] = invd;
     }
     const float T0 = __shfl(T, lane & 31);
@@ -237,7 +257,8 @@ __device__ __forceinline__ void store_half(const Dims& d, const ImageArena& im, 
 // An empty tile inside the image (W a multiple of 4): background colour, T = 1, n_contrib = 0,
 // inverse depth 0, as 16-byte stores -- lane l owns pixels 4 (l % 4) .. +3 of tile row l / 4, so each
 // store instruction writes one channel of the whole tile (a quarter of store_strip's instruction
-// count for the same bytes).
+// count for the same bytes).  FWD (forward-only): colour and inverse depth only.
+template <bool FWD = false>
 __device__ __forceinline__ void fill_tile(const Dims& d, const ImageArena& im, const Outputs& o, const float* bg,
                                           int b, int tx, int ty, int lane) {
     const int64_t HW = (int64_t)d.H * d.W;
@@ -249,9 +270,11 @@ __device__ __forceinline__ void fill_tile(const Dims& d, const ImageArena& im, c
         const unsigned v = __float_as_uint(bg[c]);
         __builtin_amdgcn_raw_buffer_store_b128((uint4x){v, v, v, v}, rs, off * 4, c * (int)HW * 4, 0);
     }
-    const unsigned one = __float_as_uint(1.0f);
-    *reinterpret_cast<uint4x*>(im.final_T + b * HW + off) = (uint4x){one, one, one, one};
-    *reinterpret_cast<uint4x*>(im.n_contrib + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
+    if (!FWD) {
+        const unsigned one = __float_as_uint(1.0f);
+        *reinterpret_cast<uint4x*>(im.final_T + b * HW + off) = (uint4x){one, one, one, one};
+        *reinterpret_cast<uint4x*>(im.n_contrib + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
+    }
     if (o.out_invdepth) *reinterpret_cast<uint4x*>(o.out_invdepth + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
 }
 
@@ -321,9 +344,10 @@ __device__ __forceinline__ void overflow_fill(const Dims& d, const Outputs& o) {
 // SPLIT: 0 = f32 MFMA (exact), 1 = split-bf16 products of per-frame features, 2 = of the batch's
 // pre-split feature table (k_split_features).  HALF: one frame, a wave per half strip.  STATS / TL:
 // the instrumented variants (gsr_render_counters / gsr_render_timeline).  ABL: timing ablations
-// (GSR_TUNING builds only).
+// (GSR_TUNING builds only).  FWD: the forward-only instantiation of the production 3-slot batched
+// kernel (GSR_FORWARD_ONLY): no last-contributor tracking, no final_T / n_contrib stores.
 template <bool EXACT, bool STATS, bool TL, bool REFINE, int ABL = 0, int SPLIT = 0, int NSLOT = 3,
-          bool HALF = false>
+          bool HALF = false, bool FWD = false>
 __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in, const GeomArena& g,
                                                 const ImageArena& im, const BinArena& bn,
                                                 const Outputs& o) {
@@ -333,6 +357,8 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
     }
     static_assert(!HALF || (!STATS && !TL && !REFINE && ABL == 0), "half-strip waves: production kernel only");
     static_assert(NSLOT == 3 || NSLOT == 5, "three or five pipeline slots");
+    static_assert(!FWD || (!STATS && !TL && !REFINE && !HALF && ABL == 0 && NSLOT == 3 && SPLIT != 1),
+                  "forward-only: the production 3-slot batched kernel only");
     const uint32_t ne = g.ctrl[kCtrlNonEmpty];
     // HALF: every strip is two work items (one wave per 32-pixel half, the strip's rows 0-3 / 4-7)
     const uint32_t nstrip = (HALF ? 2u : 1u) * (uint32_t)kStrips * ne;
@@ -367,13 +393,13 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
                        ((reinterpret_cast<uintptr_t>(o.out_color) | reinterpret_cast<uintptr_t>(o.out_invdepth)) &
                         15u) == 0 &&
                        (t % d.gx + 1) * GSR_BX <= d.W && (t / d.gx + 1) * GSR_BY <= d.H) {
-                fill_tile(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
+                fill_tile<FWD>(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
             } else {
                 for (int sp = 0; sp < kStrips; sp++) {
                     int ex0, ey0;
                     strip_origin(t % d.gx, t / d.gx, sp, ex0, ey0);
-                    store_strip<true, REFINE>(d, im, o, in.bg + in.s_bg * b, b, ex0, ey0, lane, unused, unused,
-                                              1.0f, 0.f, 0u);
+                    store_strip<true, REFINE, FWD>(d, im, o, in.bg + in.s_bg * b, b, ex0, ey0, lane, unused,
+                                                   unused, 1.0f, 0.f, 0u);
                 }
             }
             if (TL && lane == 0 && item < (o.timeline_cap & 0x7FFFFFFFu)) {  // empty tiles: k-steps 0xFFFFFFFF
@@ -412,8 +438,8 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
             const floatx16 zero = {};
             if constexpr (HALF) store_half(d, im, o, in.bg + in.s_bg * b, b, sx0, sy0 + half * (32 / kStripW), lane,
                                            zero, 1.0f, 0.f, 0u);
-            else store_strip<false, REFINE>(d, im, o, in.bg + in.s_bg * b, b, sx0, sy0, lane, zero, zero, 1.0f,
-                                            0.f, 0u);
+            else store_strip<false, REFINE, FWD>(d, im, o, in.bg + in.s_bg * b, b, sx0, sy0, lane, zero, zero,
+                                                 1.0f, 0.f, 0u);
             continue;
         }
         const uint2 range = im.ranges[tile_g];
@@ -465,7 +491,7 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
                 const int i_ = (int)__builtin_ctzll(mask);                                          \
                 mask = clear_bit(mask, i_);                                                         \
                 g_ = __builtin_amdgcn_readlane(cidx, i_) & kIndexMask;                              \
-                pos_ = base + i_ + 1;                                                               \
+                if (!FWD) pos_ = base + i_ + 1;                                                     \
             }                                                                                       \
             ok_;                                                                                    \
         })
@@ -483,8 +509,10 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
                 mask = clear_bit(mask, i1_);                                                        \
                 ga_ = __builtin_amdgcn_readlane(cidx, i0_) & kIndexMask;                            \
                 gb_ = __builtin_amdgcn_readlane(cidx, i1_) & kIndexMask;                            \
-                pa_ = base + i0_ + 1;                                                               \
-                pb_ = base + i1_ + 1;                                                               \
+                if (!FWD) {                                                                         \
+                    pa_ = base + i0_ + 1;                                                           \
+                    pb_ = base + i1_ + 1;                                                           \
+                }                                                                                   \
                 S##v = true;                                                                        \
                 S##hb = true;                                                                       \
             } else {                                                                                \
@@ -495,7 +523,7 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
                 if (!S##v) ga_ = (uint32_t)d.P;                                                     \
                 if (!S##hb) { gb_ = (uint32_t)d.P; pb_ = pa_; }                                     \
             }                                                                                       \
-            S##pa = pa_; S##pb = pb_;                                                               \
+            if (!FWD) { S##pa = pa_; S##pb = pb_; }  /* (forward-only slots carry no positions) */  \
             if (HALF) {  /* lane half h: survivor h's whole record, two 16-B loads */               \
                 const uint32_t gl_ = hi ? gb_ : ga_;                                                \
                 S##a0 = rec_load(rrs, gl_ * 32);                                                    \
@@ -581,9 +609,11 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
         } else {                                                                                    \
             const float f_ = S##f;                                                                  \
             const bool was_done_ = done;                                                            \
-            const float wa_ = take_step(S##al, S##ai, (uint32_t)S##pa, T, invd, last, done);        \
+            const float wa_ = FWD ? take_step(S##al, S##ai, T, invd, done)                          \
+                                  : take_step(S##al, S##ai, (uint32_t)S##pa, T, invd, last, done);  \
             const bool done_a_ = done;                                                              \
-            const float wb_ = take_step(S##bl, S##bi, (uint32_t)S##pb, T, invd, last, done);        \
+            const float wb_ = FWD ? take_step(S##bl, S##bi, T, invd, done)                          \
+                                  : take_step(S##bl, S##bi, (uint32_t)S##pb, T, invd, last, done);  \
             if (STATS) {                                                                            \
                 if (!was_done_ && done_a_) stop = (uint32_t)S##pa;                                  \
                 else if (!done_a_ && done) stop = (uint32_t)S##pb;                                  \
@@ -706,8 +736,8 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
         else if (ABL == 9) {  /* timing ablation: only final_T of the strip is stored */
             if (px < d.W && py < d.H) im.final_T[b * (int64_t)d.H * d.W + (int64_t)py * d.W + px] = T + acc0[0] + acc1[0];
         }
-        else store_strip<false, REFINE>(d, im, o, in.bg + in.s_bg * b, b, sx0, sy0, lane, acc0, acc1, T,
-                                        invd, last);
+        else store_strip<false, REFINE, FWD>(d, im, o, in.bg + in.s_bg * b, b, sx0, sy0, lane, acc0, acc1, T,
+                                             invd, last);
     }
 }
 
@@ -721,11 +751,12 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
 #ifndef GSR_HALF_WPE
 #define GSR_HALF_WPE 3
 #endif
-template <bool EXACT, bool STATS, bool TL, int SPLIT = 0, int NSLOT = GSR_BATCH_NSLOT, bool HALF = false>
+template <bool EXACT, bool STATS, bool TL, int SPLIT = 0, int NSLOT = GSR_BATCH_NSLOT, bool HALF = false,
+          bool FWD = false>
 __global__ __launch_bounds__(GSR_TILE_PIX)
 __attribute__((amdgpu_waves_per_eu(HALF ? GSR_HALF_WPE : GSR_RENDER_WPE))) void k_render_fwd(
     Dims d, Inputs in, GeomArena g, ImageArena im, BinArena bn, Outputs o) {
-    render_fwd_body<EXACT, STATS, TL, false, 0, SPLIT, NSLOT, HALF>(d, in, g, im, bn, o);
+    render_fwd_body<EXACT, STATS, TL, false, 0, SPLIT, NSLOT, HALF, FWD>(d, in, g, im, bn, o);
 }
 
 #ifdef GSR_TUNING
@@ -1202,9 +1233,13 @@ void launch_render_fwd(const Dims& d, const Inputs& in_, const GeomArena& g, con
         hipLaunchKernelGGL(k_split_features, dim3((d.P * GSR_C / 4 + 255) / 256), dim3(256), 0, s,
                            d.P * GSR_C / 4, reinterpret_cast<const float4*>(in.colors),
                            reinterpret_cast<uint4*>(g.fsplit));
-        GSR_LAUNCH(0, false, false, 2)
+        // forward-only (GSR_FORWARD_ONLY): the instantiation without the backward's per-pixel state
+        if (in.fwd_only) GSR_LAUNCH(0, false, false, 2, GSR_BATCH_NSLOT, false, true)
+        else GSR_LAUNCH(0, false, false, 2)
     } else if (split) {
         GSR_LAUNCH(0, false, false, 1)
+    } else if (in.fwd_only) {
+        GSR_LAUNCH(0, false, false, 0, GSR_BATCH_NSLOT, false, true)
     } else {
         GSR_LAUNCH(0, false, false)
     }

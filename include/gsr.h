@@ -72,7 +72,12 @@ const char* gsr_last_error(void);
  * render_motion.py).  Preprocess then writes only what binning and compositing read (depth, render
  * record, tile rect and count; plus the caller's radii) and skips the rows kept for the backward
  * (cov3D, means2D, conic, inverse depth, radii in the workspace): 56 of 108 bytes per visible
- * Gaussian.  Images are unchanged.  A gsr_backward_batch* on a workspace whose last forward was
+ * Gaussian.  The batched compositing kernel (two frames or more, without the refiner epilogue)
+ * then runs its forward-only instantiation, which neither tracks a pixel's last contributor nor
+ * stores final_T and n_contrib: 132 instead of 140 bytes per pixel.  After such a call the image
+ * arena's final_T and n_contrib rows are UNSPECIFIED (whatever an earlier call left there); the
+ * next forward without the flag rewrites every pixel of both.  Images are unchanged.  A
+ * gsr_backward_batch* on a workspace whose last forward was
  * forward-only fails with GSR_ERR_ARG (the library records it per workspace pointer on the host;
  * the kernels also skip such a workspace, so nothing is computed either way). */
 #define GSR_FORWARD_ONLY 0x100u
