@@ -26,7 +26,10 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_pack_rows", "gsr_deform_gaussians", "gsr_ehm_workspace_bytes", "gsr_ehm_forward",
            "gsr_deform_gaussians_backward", "gsr_backward_batch_deformed",
            # include/gsr_ssim.h
-           "gsr_fused_ssim", "gsr_fused_ssim_backward", "gsr_image_loss_partials", "gsr_image_loss")
+           "gsr_fused_ssim", "gsr_fused_ssim_backward", "gsr_image_loss_partials", "gsr_image_loss",
+           # include/gsr_loss.h
+           "gsr_guava_loss_workspace_bytes", "gsr_guava_loss_partials", "gsr_guava_loss_forward",
+           "gsr_guava_loss_backward", "gsr_uv_regularizers_partials", "gsr_uv_regularizers")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -285,6 +288,19 @@ def load(path=None):
     L.gsr_image_loss_partials.restype = _i
     L.gsr_image_loss.argtypes = [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
     L.gsr_image_loss.restype = _i
+    L.gsr_guava_loss_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
+    L.gsr_guava_loss_workspace_bytes.restype = _sz
+    L.gsr_guava_loss_partials.argtypes = [_i, _i, _i, _i, _i]
+    L.gsr_guava_loss_partials.restype = _i
+    L.gsr_guava_loss_forward.argtypes = [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _f, _i, _i, _i, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]
+    L.gsr_guava_loss_forward.restype = _i
+    L.gsr_guava_loss_backward.argtypes = [_i, _i, _i, _vp, _f, _f, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.gsr_guava_loss_backward.restype = _i
+    L.gsr_uv_regularizers_partials.argtypes = [_i]
+    L.gsr_uv_regularizers_partials.restype = _i
+    L.gsr_uv_regularizers.argtypes = [_i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp]
+    L.gsr_uv_regularizers.restype = _i
     _lib = L
     return L
 

@@ -5,6 +5,7 @@
  *   gsr_fused_ssim          <- fusedssim()          ssim.cu:368-404 (kernel fusedssimCUDA :187-286)
  *   gsr_fused_ssim_backward <- fusedssim_backward() ssim.cu:406-444 (kernel :288-366)
  *   gsr_image_loss          <- the L1 terms of the training loss and their gradient (utils/loss_utils.py)
+ * (the loss's foreground mask, head / hand crop terms and regularisers: include/gsr_loss.h)
  * Python front-end with the reference's API (FusedSSIMMap, fused_ssim): guava_renderer_amd/fused_ssim.
  *
  * Images are [B, CH, H, W] float32 device arrays (contiguous).  The 11x11 Gaussian window

@@ -8,7 +8,11 @@
              config 4) in alternating blocks: the difference is the price of posing;
   profile    a few AvatarTrainer steps and standalone assembly backwards, for a
              `rocprofv3 --kernel-trace --stats -- python tools/avatar_train_bench.py --mode profile`
-             run (kernel times of k_preprocess_bwd_deformed and k_deform_gaussians_bwd).
+             run (kernel times of k_preprocess_bwd_deformed and k_deform_gaussians_bwd);
+  --guava-loss   (instead of --mode) GUAVA's mask / head and hand crop / regulariser loss terms at
+             config 4's shape (B=6, 512 x 512, crops resampled to 256): the loss stage, fused kernels
+             against the torch-autograd chain of the same terms, and the whole step with and without
+             the terms.
 
     python tools/avatar_train_bench.py --mode backward --B 6
 Prints one JSON line per measurement.  Times are device-event times of blocks of `--reps` calls."""
@@ -127,7 +131,7 @@ def bench_backward(B, a):
     report("backward_deformed vs composed", B, timed_blocks(fns, a.reps, a.rounds, a.warmup))
 
 
-def avatar_trainer(B):
+def avatar_trainer(B, reg=None):
     va, ua, faces, verts, T = posed_avatar(B)
     views, projs, tanf = cameras(B)
     dfm = deform.GaussianDeformer(va, ua, faces, apply_rgb_sigmoid=False)
@@ -140,7 +144,7 @@ def avatar_trainer(B):
     del probe, d
     torch.cuda.empty_cache()
     tr = AvatarTrainer(va, ua, faces, B, W, W, R_capacity=int(R * 2) + 1024, device=DEV, lr=1e-5,
-                       apply_rgb_sigmoid=False)
+                       apply_rgb_sigmoid=False, reg=reg)
     target = torch.rand((B, 3, W, W), device=DEV, generator=torch.Generator(device=DEV).manual_seed(0))
     return tr, lambda: tr.step(verts, T, views, projs, tanf, target)
 
@@ -192,13 +196,81 @@ def profile(B, a):
     print(json.dumps({"measurement": "profile run", "B": B, "steps": a.warmup + a.reps}), flush=True)
 
 
+def guava_batch(B):
+    """The fields of a GUAVA batch beside the poses: image, a soft foreground mask (an ellipse with a
+    feathered edge) and the three boxes of plausible size, jittered per frame (int64 [3,B,4], as the
+    reference's loader gives them): head ~150 x 150, each hand ~60 x 60."""
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    target = torch.rand((B, 3, W, W), device=DEV, generator=gen)
+    y, x = torch.meshgrid(torch.arange(W, device=DEV), torch.arange(W, device=DEV), indexing="ij")
+    r = (((x - W / 2) / (0.28 * W)) ** 2 + ((y - W / 2) / (0.45 * W)) ** 2).sqrt()
+    mask = ((1.15 - r) / 0.3).clamp(0, 1).expand(B, 1, W, W).contiguous()
+    rng = np.random.default_rng(0)
+    boxes = np.zeros((3, B, 4), np.int64)
+    for g, (cx, cy, size) in enumerate(((256, 110, 150), (130, 330, 60), (380, 340, 60))):
+        for b in range(B):
+            jx, jy, js = rng.integers(-12, 13), rng.integers(-12, 13), rng.integers(-6, 7)
+            half = (size + js) // 2
+            boxes[g, b] = (cx + jx - half, cx + jx + half, cy + jy - half, cy + jy + half)
+    return target, mask, torch.from_numpy(boxes)
+
+
+def bench_guava_loss(B, a):
+    """--guava-loss: (1) the loss stage alone on one rendered batch -- the fused path
+    (gsr_guava_loss_forward / _backward + fused_ssim) against the torch-autograd chain of the same
+    terms (SplatTrainer.loss: a Python loop of slices, F.interpolate, cat, with the same fused_ssim)
+    -- and (2) AvatarTrainer.step with and without the mask, crop and regulariser terms."""
+    target, mask, boxes = guava_batch(B)
+    tr, plain_step = avatar_trainer(B)
+    tg, _ = avatar_trainer(B, reg=AvatarTrainer.GUAVA_REG)
+    va, ua, faces, verts, T = posed_avatar(B)
+    views, projs, tanf = cameras(B)
+    boxes_dev = boxes.to(DEV)
+    tg.gradients(verts, T, views, projs, tanf, target)
+    col = tg.rast.out_color.detach().clone()
+    torch.cuda.synchronize()
+
+    def fused():
+        return tg._guava_loss_and_image_grad(col, target, mask, boxes_dev, True)
+
+    def chain():
+        feat = col.detach().requires_grad_(True)
+        loss = tg.loss(feat, target, mask=mask, boxes=boxes, mask_refined=True)  # (boxes on the host: no sync)
+        loss.backward()
+        return loss.detach(), feat.grad
+
+    (lf, gf), (lc, gc) = fused(), chain()
+    torch.cuda.synchronize()
+    # (two float32 evaluations of W . feat may put a difference on either side of L1's kink: a
+    # handful of elements may differ by a whole sign, so the agreement is a fraction of elements)
+    err = float(((gf - gc).abs() > 1e-3 * gc.abs().max()).float().mean())
+    assert abs(lf.item() - lc.item()) <= 1e-4 * abs(lc.item()) and err <= 1e-4, (lf.item(), lc.item(), err)
+    row = {"loss_fused": lf.item(), "loss_torch_chain": lc.item(), "grad_fraction_off_by_1e-3_of_max": err}
+    print(json.dumps({"measurement": "guava loss agreement", **row}), flush=True)
+    report("guava loss stage: fused vs torch chain", B,
+           timed_blocks({"fused_loss": fused, "torch_chain_loss": chain}, a.reps, a.rounds, a.warmup))
+
+    def guava_step():
+        return tg.step(verts, T, views, projs, tanf, target, mask=mask, boxes=boxes_dev, mask_refined=True)
+    report("AvatarTrainer.step: guava loss terms vs whole-frame loss", B,
+           timed_blocks({"guava_step": guava_step, "plain_step": plain_step}, a.reps, a.rounds, a.warmup))
+    assert tr.skipped_steps == 0 and tg.skipped_steps == 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("backward", "step", "profile"), required=True)
+    ap.add_argument("--mode", choices=("backward", "step", "profile"))
+    ap.add_argument("--guava-loss", action="store_true",
+                    help="time GUAVA's mask / crop / regulariser loss terms (instead of --mode)")
     ap.add_argument("--B", type=int, default=6)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
+    if a.guava_loss == (a.mode is not None):
+        ap.error("give --mode or --guava-loss")
     assert torch.cuda.is_available(), "needs a HIP device"
-    {"backward": bench_backward, "step": bench_step, "profile": profile}[a.mode](a.B, a)
+    if a.guava_loss:
+        bench_guava_loss(a.B, a)
+    else:
+        {"backward": bench_backward, "step": bench_step, "profile": profile}[a.mode](a.B, a)
