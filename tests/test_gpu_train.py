@@ -307,3 +307,51 @@ def test_image_loss_kernel_matches_autograd():
         torch.cuda.synchronize()
         assert abs(part.sum().item() - ref.item()) <= 1e-5 * abs(ref.item())
         np.testing.assert_allclose(dL.cpu().double().numpy(), g.numpy(), atol=1e-9, rtol=1e-5)
+
+
+def _image_loss_inputs(B, H, W):
+    """CPU float32 inputs of gsr_image_loss at a ragged size (seeded by the shape)."""
+    gen = torch.Generator().manual_seed(1000 * B + 37 * H + W)
+    feat = torch.rand((B, 32, H, W), generator=gen)
+    tgt = torch.rand((B, 3, H, W), generator=gen)
+    extra = torch.randn((B, 3, H, W), generator=gen) * 1e-3
+    rw = (torch.rand((3, 32), generator=gen) * 2 - 1) / 32 ** 0.5
+    return feat, tgt, extra, rw
+
+
+@pytest.mark.parametrize("B,H,W", [(1, 1, 1), (2, 15, 17), (1, 1, 257), (3, 37, 53)])
+@pytest.mark.parametrize("use_rw", [True, False])
+@pytest.mark.parametrize("use_extra", [True, False])
+def test_image_loss_kernel_ragged_sizes(B, H, W, use_rw, use_extra):
+    """gsr_image_loss where H*W is no multiple of the 256-thread workgroup (1, 255, 257, 1961): the
+    last workgroup's idle lanes add nothing to its partial and write nothing.  Outputs start as NaN;
+    bars and float64 reference as test_image_loss_kernel_matches_autograd."""
+    import ctypes
+    from guava_renderer_amd import _lib
+    feat, tgt, extra, rw = _image_loss_inputs(B, H, W)
+    f = feat.double().requires_grad_(True)
+    t = tgt.double()
+    diffs = [f[:, :3] - t]
+    if use_rw:
+        diffs.append(torch.einsum("oc,bchw->bohw", rw.double(), f) - t)
+    margin = min(d.abs().min().item() for d in diffs)
+    assert margin >= 1e-6, f"inputs: a difference of {margin:.3g} sits on L1's kink (pick another seed)"
+    ref = 0.8 * diffs[0].abs().mean() + (diffs[1].abs().mean() if use_rw else 0.0)
+    ref.backward()
+    g = f.grad.clone()
+    if use_extra:
+        g[:, :3] += extra.double()
+    L = _lib.load()
+    n_part = L.gsr_image_loss_partials(B, H, W)
+    assert n_part == B * ((H * W + 255) // 256)
+    d_feat, d_tgt, d_extra, d_rw = (x.to(DEV) for x in (feat, tgt, extra, rw))
+    part = torch.full((n_part,), float("nan"), device=DEV)
+    dL = torch.full_like(d_feat, float("nan"))
+    _lib.check(L.gsr_image_loss(B, H, W, d_feat.data_ptr(), d_tgt.data_ptr(), d_rw.data_ptr() if use_rw else None,
+                                0.8, 1.0 if use_rw else 0.0, d_extra.data_ptr() if use_extra else None,
+                                dL.data_ptr(), part.data_ptr(),
+                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_image_loss")
+    torch.cuda.synchronize()
+    assert part.numel() == n_part and bool(torch.isfinite(part).all())
+    assert abs(part.sum().item() - ref.item()) <= 1e-5 * abs(ref.item())
+    np.testing.assert_allclose(dL.cpu().double().numpy(), g.numpy(), atol=1e-9, rtol=1e-5)
