@@ -183,14 +183,175 @@ def operand_scene(row):
     return d, dL, dLinv, mod, aa
 
 
+# ------------------------------------------------------------------ wide-angle and close cameras
+#
+# camera.camera has tanfovx == tanfovy == 1/24 at distance 22: on every scene above |t.x / t.z| stays
+# below 0.73 (x) / 0.955 (y) of the EWA limit 1.3 tanfov, no Gaussian is nearer than z = 21, and the
+# perspective column of the projection's Jacobian carries next to nothing.  The two scenes below
+# leave that regime; tests/test_oracle.py pins the oracle on them against float64 autograd and
+# tests/test_gpu_wide_camera.py the GPU.
+
+def fov_camera(W, H, tanfovx, tanfovy, yaw=0.0, pitch=0.0, distance=22.0):
+    """camera.camera with a field of view per axis: the view of camera.look_at_w2c, the projection
+    get_proj_matrix(1.0) with P[0,0] = 1 / tanfovx and P[1,1] = 1 / tanfovy."""
+    from guava_renderer_amd import camera
+    w2c = camera.look_at_w2c(yaw, pitch, distance)
+    view = camera.get_view_matrix(w2c[:3, :3], w2c[:3, 3]).T.copy()
+    proj = camera.get_proj_matrix(1.0)
+    proj[0, 0] = np.float32(1.0) / np.float32(tanfovx)
+    proj[1, 1] = np.float32(1.0) / np.float32(tanfovy)
+    full = (view @ proj.T.copy()).astype(np.float32)
+    c2w = np.linalg.inv(w2c.astype(np.float64)).astype(np.float32)
+    return dict(image_height=int(H), image_width=int(W), tanfovx=float(np.float32(tanfovx)),
+                tanfovy=float(np.float32(tanfovy)), viewmatrix=view, projmatrix=full, campos=c2w[:3, 3].copy())
+
+
+def world_z_for_view_z(d, m, zv):
+    """World z that puts points (x, y from m) at view-space depth zv (row-vector view matrix,
+    graphics_utils.py:44-50 layout: z_view = x V[0][2] + y V[1][2] + z V[2][2] + V[3][2])."""
+    V = d["viewmatrix"].astype(np.float64).reshape(4, 4)
+    z = (zv - m[:, 0] * V[0, 2] - m[:, 1] * V[1, 2] - V[3, 2]) / V[2, 2]
+    return z.astype(np.float32)
+
+
+def view_space(d):
+    """float64 view-space positions [P,3] of the scene's means."""
+    V = d["viewmatrix"].astype(np.float64).reshape(4, 4)
+    return d["means3D"].astype(np.float64) @ V[:3, :3] + V[3, :3]
+
+
+def _bg_and_cotangents(W, H, seed=3):
+    rng = np.random.default_rng(seed)
+    bg = rng.uniform(-1.0, 2.0, C).astype(np.float32)
+    dL = rng.normal(size=(C, H, W)).astype(np.float32)
+    dLinv = rng.normal(size=(1, H, W)).astype(np.float32)
+    return bg, dL, dLinv
+
+
+WIDE_TANFOV = (0.8, 0.5)
+WIDE_CAMERA = dict(distance=1.6, yaw=0.3, pitch=-0.2)
+
+
+def wide_cloud(P=400, seed=5):
+    """scenes.random_cloud spread over x in +-2.0, y in -0.6 +- 1.3, z in +-0.5 (beyond both EWA limits
+    of a camera at distance 1.6 with tanfov (0.8, 0.5)), the first 15% of the Gaussians large (scales
+    0.125..0.25: footprints of a hundred pixels), and quaternions of norm 0.6..1.6 (the reference does
+    not normalise them)."""
+    from guava_renderer_amd import scenes
+    d = scenes.random_cloud(P, seed)
+    rng = np.random.default_rng(seed + 1)
+    m = d["means3D"]
+    m[:, 0] = rng.uniform(-2.0, 2.0, P)
+    m[:, 1] = rng.uniform(-1.3, 1.3, P) - 0.6
+    m[:, 2] = rng.uniform(-0.5, 0.5, P)
+    n_big = (3 * P) // 20
+    d["scales"][:n_big] = (rng.uniform(0.5, 1.0, (n_big, 3)) * 0.25).astype(np.float32)
+    d["rotations"] = (d["rotations"] * rng.uniform(0.6, 1.6, (P, 1))).astype(np.float32)
+    return d
+
+
+def wide_scene(P=400, W=64, H=48, seed=5):
+    """Scene "wide": wide_cloud under fov_camera(tanfov (0.8, 0.5), distance 1.6, yaw 0.3, pitch -0.2)
+    -> (scene dict with a non-zero bg, dL[C,H,W], dLinv[1,H,W])."""
+    d = wide_cloud(P, seed)
+    d.update(fov_camera(W, H, *WIDE_TANFOV, **WIDE_CAMERA))
+    d["bg"], dL, dLinv = _bg_and_cotangents(W, H)
+    return d, dL, dLinv
+
+
+NEAR_PLANE = np.float32(0.2)   # in_frustum culls view z <= 0.2f (auxiliary.h:151-176)
+NEAR_LADDER = 20               # rows of near_scene placed around the near plane
+NEAR_CLOSE = 60                # rows behind them placed on screen at view z 0.205..0.4
+
+
+def near_scene(P=500, W=50, H=38, seed=8):
+    """Scene "near": a cloud of small Gaussians around a camera half a unit from its centre (tanfov
+    0.6), so that a quarter of them lie behind the near plane.
+    The first NEAR_LADDER rows sit near the optical axis at view depths around 0.2f, nextafter(0.2f)
+    on both sides, and 0.21: for each of the four depths, the five consecutive float32 world z
+    around the solution of world_z_for_view_z (the view transform rounds, so a single solve need not
+    land on the depth it aims at; the ladder's steps are smaller than 3 ulp of 0.2f in view z).
+    The next NEAR_CLOSE rows are on screen at view z 0.205..0.4.
+    The features are halved and the seed chosen so that the oracle's f32 image error against float64
+    (rounding of the means amplified by focal / z; 0.8e-5..1.9e-5 over seeds 6..17 even so) stays a
+    factor two inside test_oracle._torch_check's 2e-5: 9.8e-6 at this seed.
+    -> (scene dict with a non-zero bg, dL, dLinv)."""
+    from guava_renderer_amd import scenes
+    d = scenes.random_cloud(P, seed)
+    rng = np.random.default_rng(seed + 1)
+    m = d["means3D"]
+    m[:, 0] = rng.uniform(-0.5, 0.5, P)
+    m[:, 1] = rng.uniform(-0.4, 0.4, P) - 0.6
+    m[:, 2] = rng.uniform(-0.6, 0.6, P)
+    d["scales"] = (d["scales"] * np.float32(0.15)).astype(np.float32)
+    d.update(fov_camera(W, H, 0.6, 0.6, yaw=-0.2, pitch=0.1, distance=0.5))
+    n = NEAR_LADDER
+    targets = np.repeat(np.array([NEAR_PLANE, np.nextafter(NEAR_PLANE, np.float32(-1)),
+                                  np.nextafter(NEAR_PLANE, np.float32(1)), np.float32(0.21)], np.float64), n // 4)
+    V = d["viewmatrix"].astype(np.float64).reshape(4, 4)
+    tv = np.stack([rng.uniform(-0.05, 0.05, n), rng.uniform(-0.04, 0.04, n), targets], 1)
+    m[:n] = ((tv - V[3, :3]) @ np.linalg.inv(V[:3, :3])).astype(np.float32)
+    z = world_z_for_view_z(d, m[:n], targets)
+    for _ in range(2):
+        z = np.nextafter(z, np.float32(-np.inf))
+    for k in range(n):
+        for _ in range(k % 5):
+            z[k] = np.nextafter(z[k], np.float32(np.inf))
+    m[:n, 2] = z
+    # on screen just behind the plane: where 1 / t.z^2 and 1 / t.z^3 of the backward are largest
+    k = NEAR_CLOSE
+    zc = rng.uniform(0.205, 0.4, k)
+    tc = np.stack([rng.uniform(-0.5, 0.5, k) * zc, rng.uniform(-0.5, 0.5, k) * zc, zc], 1)
+    m[n:n + k] = ((tc - V[3, :3]) @ np.linalg.inv(V[:3, :3])).astype(np.float32)
+    d["colors"] = (d["colors"] * np.float32(0.5)).astype(np.float32)
+    d["bg"], dL, dLinv = _bg_and_cotangents(W, H)
+    return d, dL, dLinv
+
+
+def wide_conditions(d, radii, g_means3D):
+    """What scene "wide" must provide, from the oracle's radii and the float64 means3D gradient alone
+    (asserted): -> the counts, for the record."""
+    t = view_space(d)
+    ax, ay = np.abs(t[:, 0] / t[:, 2]), np.abs(t[:, 1] / t[:, 2])
+    lx, ly = 1.3 * d["tanfovx"], 1.3 * d["tanfovy"]
+    vis = np.asarray(radii) > 0
+    cx, cy = ax > lx, ay > ly
+    big = np.abs(g_means3D).max(1) >= 1e-2 * np.abs(g_means3D).max()
+    n = dict(visible=int(vis.sum()), clamped=int((vis & (cx | cy)).sum()),
+             clamped_with_gradient=int((vis & (cx | cy) & big).sum()),
+             clamped_one_axis=int((vis & (cx ^ cy)).sum()),
+             swap_changes_decision=int((vis & ((cx != (ax > ly)) | (cy != (ay > lx)))).sum()))
+    print("  wide scene: " + ", ".join(f"{k} {v}" for k, v in n.items()))
+    assert n["clamped_with_gradient"] >= 10 and n["clamped_one_axis"] >= 10 and n["swap_changes_decision"] >= 10, n
+    return n
+
+
+def near_conditions(d, radii):
+    """What scene "near" must provide, from the oracle's radii alone (asserted): at least 50 Gaussians
+    culled by the near plane, at least 50 visible ones nearer than z = 0.4, and among the ladder rows
+    both culled and visible ones with the nearest visible within 4 ulp of 0.2f."""
+    z = view_space(d)[:, 2]
+    vis = np.asarray(radii) > 0
+    assert not vis[z <= 0.2 - 1e-6].any()
+    lad = np.arange(len(z)) < NEAR_LADDER
+    n = dict(visible=int(vis.sum()), culled_by_near_plane=int((z <= 0.2 - 1e-6).sum()),
+             visible_below_0p4=int((vis & (z < 0.4)).sum()), ladder_visible=int((vis & lad).sum()),
+             ladder_culled=int((~vis & lad).sum()), nearest_visible=float(z[vis].min()))
+    print("  near scene: " + ", ".join(f"{k} {v}" for k, v in n.items()))
+    assert n["culled_by_near_plane"] >= 50 and n["visible_below_0p4"] >= 50, n
+    assert n["ladder_visible"] >= 5 and n["ladder_culled"] >= 5, n
+    assert n["nearest_visible"] <= float(NEAR_PLANE) + 4 * float(np.spacing(NEAR_PLANE)), n
+    return n
+
+
 F64_NAMES = ("colors", "opacity", "means3D", "scales", "rotations", "means2D")
 
 
-def float64_reference(d, st, dL=None, dLinv=None, scale_modifier=1.0, antialiasing=False):
+def float64_reference(d, st, dL=None, dLinv=None, scale_modifier=1.0, antialiasing=False, **switches):
     """tests/torch_ref.py on the scene, over the tile lists of the oracle state `st`: (image
     [C,H,W], n_contrib [H*W], gradients by F64_NAMES or None without dL), numpy float64.  "scales" is
     the gradient w.r.t. scale_modifier * scales and "means2D" the NDC one, as the reference returns
-    them (torch_ref's docstring)."""
+    them (torch_ref's docstring).  switches: torch_ref.project's clamp= and diagonal_J=."""
     import torch
     import torch_ref
     W, H = d["image_width"], d["image_height"]
@@ -202,7 +363,7 @@ def float64_reference(d, st, dL=None, dLinv=None, scale_modifier=1.0, antialiasi
     pr = torch_ref.project(m3, sc, rot, torch.tensor(d["viewmatrix"], dtype=torch.float64),
                            torch.tensor(d["projmatrix"], dtype=torch.float64), W, H, float(d["tanfovx"]),
                            float(d["tanfovy"]), scale_mod=float(scale_modifier), ndc_offset=off,
-                           antialiasing=antialiasing)
+                           antialiasing=antialiasing, **switches)
     out, inv, _, nc = torch_ref.render(pr, op * pr["o1"], colr, torch.tensor(d["bg"], dtype=torch.float64),
                                        W, H, tile_lists)
     grads = None

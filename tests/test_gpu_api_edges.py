@@ -14,18 +14,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_scene, torch_inputs
+from helpers import make_scene, torch_inputs, world_z_for_view_z as _world_z_for_view_z
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def _world_z_for_view_z(d, m, zv):
-    """World z that puts points (x, y from m) at view-space depth zv (row-vector view matrix,
-    graphics_utils.py:44-50 layout: z_view = x V[0][2] + y V[1][2] + z V[2][2] + V[3][2])."""
-    V = d["viewmatrix"].astype(np.float64).reshape(4, 4)
-    z = (zv - m[:, 0] * V[0, 2] - m[:, 1] * V[1, 2] - V[3, 2]) / V[2, 2]
-    return z.astype(np.float32)
 
 
 def test_mark_visible_bit_exact():

@@ -224,6 +224,72 @@ def test_operand_axes_match_float64_autograd(row):
     _torch_check(d, d["image_width"], d["image_height"], dL, dLinv, scale_modifier=mod, antialiasing=aa)
 
 
+SENSITIVITY = 1e-2  # of scale, as tests/test_gpu_operands.py: 100x the GPU's gradient bar
+
+
+def _switch_effect(d, dL, dLinv, aa, ref, **switch):
+    """float64 alone: how far the means3D / scales / rotations gradients move under torch_ref.project's
+    switch, of the unswitched gradients' scale."""
+    _, _, _, st = _fwd(d, antialiasing=aa)
+    _, _, other = float64_reference(d, st, dL, dLinv, antialiasing=aa, **switch)
+    e = {k: scale_err(other[k], ref[k]) for k in ("means3D", "scales", "rotations")}
+    print(f"  sensitivity: {switch} moves " + ", ".join(f"{k} by {v:.3g}" for k, v in e.items()) + " of scale")
+    return e, other
+
+
+@pytest.mark.parametrize("aa", [False, True], ids=["plain", "aa"])
+def test_wide_camera_matches_float64_autograd(aa):
+    """helpers.wide_scene: tanfovx != tanfovy, Gaussians beyond the EWA limit of either axis or both
+    (computeCov2D's clamp and x_grad_mul / y_grad_mul of its backward), a perspective column of J that
+    carries a third of the gradient, non-unit quaternions.  The scene's conditions, then the oracle's
+    image and every gradient against float64 autograd at _torch_check's bars, then from float64
+    alone: without the clamp, with the two limits swapped, or without J's perspective column the
+    gradients move by >= SENSITIVITY; and autograd through clamp(t.x / t.z) * t.z (which
+    differentiates the clamped value, as this file's reference did before it was corrected) is not
+    what the oracle computes."""
+    from helpers import wide_conditions, wide_scene
+    d, dL, dLinv = wide_scene()
+    W, H = d["image_width"], d["image_height"]
+    assert np.abs(d["bg"]).min() > 0 and d["tanfovx"] != d["tanfovy"]
+    _, radii, _, st = _fwd(d, antialiasing=aa)
+    _, nc, ref = float64_reference(d, st, dL, dLinv, antialiasing=aa)
+    assert (nc == st["n_contrib"]).all()
+    wide_conditions(d, radii, ref["means3D"])
+    _torch_check(d, W, H, dL, dLinv, antialiasing=aa)
+    for switch in (dict(clamp="none"), dict(clamp="swapped"), dict(diagonal_J=True)):
+        e, _ = _switch_effect(d, dL, dLinv, aa, ref, **switch)
+        assert min(e.values()) >= SENSITIVITY, (switch, e)
+    e, old = _switch_effect(d, dL, dLinv, aa, ref, clamp="differentiated")
+    g = oracle.backward(st, d["means3D"], d["colors"], d["opacities"], d["scales"], d["rotations"], None,
+                        d["viewmatrix"], d["projmatrix"], W, H, d["tanfovx"], d["tanfovy"], d["bg"], dL, dLinv,
+                        antialiasing=aa)
+    err = scale_err(g[3], old["means3D"])
+    print(f"  oracle means3D vs autograd through the clamped value: {err:.3g} of scale")
+    assert err >= SENSITIVITY and e["means3D"] >= SENSITIVITY, (err, e)
+
+
+def test_near_camera_matches_float64_autograd():
+    """helpers.near_scene: Gaussians on both sides of the near plane in one frame, a hundred visible
+    ones at z 0.2..0.4 (1 / t.z^2, 1 / t.z^3 of the backward 10^4 times the canonical camera's), rows
+    within a few ulp of z = 0.2f.  Conditions, the oracle against float64 autograd, zero gradient rows
+    for every culled Gaussian, and the perspective column's share of the gradient."""
+    from helpers import near_conditions, near_scene
+    d, dL, dLinv = near_scene()
+    W, H = d["image_width"], d["image_height"]
+    _, radii, _, st = _fwd(d)
+    _, nc, ref = float64_reference(d, st, dL, dLinv)
+    assert (nc == st["n_contrib"]).all()
+    near_conditions(d, radii)
+    _torch_check(d, W, H, dL, dLinv)
+    g = oracle.backward(st, d["means3D"], d["colors"], d["opacities"], d["scales"], d["rotations"], None,
+                        d["viewmatrix"], d["projmatrix"], W, H, d["tanfovx"], d["tanfovy"], d["bg"], dL, dLinv)
+    for a in g:
+        if a.size:
+            assert not a.reshape(len(radii), -1)[radii == 0].any()
+    e, _ = _switch_effect(d, dL, dLinv, False, ref, diagonal_J=True)
+    assert min(e.values()) >= SENSITIVITY, e
+
+
 def test_avatar_forward_matches_float64_restatement():
     W, H = 64, 48
     d = make_scene("avatar", 400, W, H, seed=24)

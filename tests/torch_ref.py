@@ -7,7 +7,10 @@ relative) because the reference ships no tests or golden vectors for this path.
 
 Reference quirks reproduced so that autograd equals the reference's hand-written backward:
   * alpha = min(0.99, o*G) with the gradient of o*G (backward.cu:619, 635 ignore the clamp);
-  * the EWA clamp of t.xy zeroes the gradient outside the limits (backward.cu:182-183);
+  * the EWA clamp: outside the limits t.x (t.y) is replaced by lim * t.z, and the backward takes that
+    value as a constant -- dL/dt.x (dL/dt.y) is zero (x_grad_mul, y_grad_mul, backward.cu:182-183)
+    and dJ/dt.z is evaluated at the clamped t.x, t.y without differentiating lim * t.z
+    (backward.cu:310-312): project() detaches the clamped value;
   * dL/dmeans2D is the gradient w.r.t. the NDC position (ddelx_dx = W/2, backward.cu:527);
   * tile membership (the discrete rect test) is taken as given;
   * dL/dscales is the gradient w.r.t. the effective scale s = scale_mod * scales, with no factor
@@ -62,10 +65,29 @@ def _tr(A):
     return A.transpose(-1, -2)
 
 
+CLAMPS = ("reference", "none", "swapped", "differentiated")
+
+
+def _ewa_clamp(t, tz, lim, mode):
+    if mode == "none":
+        return t
+    c = torch.clamp(t / tz, -lim, lim) * tz
+    if mode == "differentiated":
+        return c
+    return torch.where(torch.abs(t / tz) > lim, c.detach(), t)
+
+
 def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=1.0, ndc_offset=None,
-            antialiasing=False):
+            antialiasing=False, clamp="reference", diagonal_J=False):
     """Per-Gaussian projection. Returns dict of tensors (float64): "o1" is the factor on the opacity
-    (h under antialiasing, else 1), "scales_eff" the effective scale scale_mod * scales."""
+    (h under antialiasing, else 1), "scales_eff" the effective scale scale_mod * scales.
+
+    Switches for sensitivity checks (the defaults are the reference):
+      clamp "none": t.xy as they are; "swapped": the x limit on t.y and the y limit on t.x;
+            "differentiated": clamp(t.x / t.z) * t.z with plain autograd, which differentiates the
+            clamped value lim * t.z w.r.t. t.z -- not what the reference's backward does;
+      diagonal_J: the Jacobian without its perspective column (J02 = J12 = 0)."""
+    assert clamp in CLAMPS, clamp
     V = view.reshape(4, 4)
     Pm = proj.reshape(4, 4)
     p = means3D
@@ -93,9 +115,13 @@ def project(means3D, scales, rotations, view, proj, W, H, tanx, tany, scale_mod=
     fy = H / (2.0 * tany)
     t = pv
     limx, limy = 1.3 * tanx, 1.3 * tany
-    tx = torch.clamp(t[:, 0] / t[:, 2], -limx, limx) * t[:, 2]
-    ty = torch.clamp(t[:, 1] / t[:, 2], -limy, limy) * t[:, 2]
+    if clamp == "swapped":
+        limx, limy = limy, limx
     tz = t[:, 2]
+    tx = _ewa_clamp(t[:, 0], tz, limx, clamp)
+    ty = _ewa_clamp(t[:, 1], tz, limy, clamp)
+    if diagonal_J:
+        tx, ty = z0, z0
     J = _glm(fx / tz, z0, -(fx * tx) / (tz * tz), z0, fy / tz, -(fy * ty) / (tz * tz), z0, z0, z0)
     Wm = _glm(*[V.reshape(-1)[k].expand_as(z0) for k in (0, 4, 8, 1, 5, 9, 2, 6, 10)])
     T = _mul(Wm, J)
