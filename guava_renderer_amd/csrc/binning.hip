@@ -21,6 +21,8 @@
 //                          stable rank = tile base + chunk base + earlier slots covering the tile
 //                          (popcount of row/column ballots), plus the exact 4-bit strip mask
 // Traffic per instance: 4 B point_list + 1 B strip mask written once; per Gaussian a few words.
+#include <algorithm>
+
 #include "gsr_cull.h"
 #include "gsr_internal.h"
 
@@ -785,9 +787,14 @@ __global__ __launch_bounds__(64 * kColWaves) void k_column_scan_wide(Dims d, Geo
     }
 }
 
+// dynamic LDS of k_chunk_count (the difference array) and of k_ordered_scatter (column and row
+// ballot words, then the per-tile bases)
+static size_t chunk_count_lds(const Dims& d) { return (size_t)(d.gx + 1) * (d.gy + 1) * 4; }
+static size_t scatter_lds(const Dims& d) { return (size_t)(d.gx + d.gy) * 4 * 8 + (size_t)d.T * 4; }
+
 void launch_chunk_count(const Dims& d, const GeomArena& g, const ImageArena& im, hipStream_t s) {
     if (d.P == 0 || d.B == 0) return;
-    const size_t lds = (size_t)(d.gx + 1) * (d.gy + 1) * 4;
+    const size_t lds = chunk_count_lds(d);
     static size_t attr = 0;
     if (lds > 65536 && attr < lds) {
         attr = lds;
@@ -829,6 +836,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(Dims d, GeomArena g, ImageAr
     }
     __syncthreads();
     if (threadIdx.x < kLptBuckets) im.lpt_hist[b * kLptBuckets + threadIdx.x] = h[threadIdx.x];
+    if (threadIdx.x == 0) g.fstat[kFsWords * b + kFsNonEmpty] = (uint32_t)d.T - h[kLptBuckets - 1];
 }
 
 __global__ __launch_bounds__(1024) void k_tile_place(Dims d, GeomArena g, ImageArena im) {
@@ -895,7 +903,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan_place1(Dims d, GeomArena g, 
         uint32_t acc = 0;
         for (int bk = 0; bk < kLptBuckets; bk++) {
             const uint32_t t = h[bk];
-            if (bk == kLptBuckets - 1) g.ctrl[kCtrlNonEmpty] = acc;
+            if (bk == kLptBuckets - 1) g.ctrl[kCtrlNonEmpty] = g.fstat[kFsNonEmpty] = acc;
             h[bk] = acc;
             acc += t;
         }
@@ -936,7 +944,7 @@ __device__ void tile_scan_place_wg(const Dims& d, const GeomArena& g, const Imag
         uint32_t acc = 0;
         for (int bk = 0; bk < kLptBuckets; bk++) {
             const uint32_t t = h[bk];
-            if (bk == kLptBuckets - 1) g.ctrl[kCtrlNonEmpty] = acc;
+            if (bk == kLptBuckets - 1) g.ctrl[kCtrlNonEmpty] = g.fstat[kFsNonEmpty] = acc;
             h[bk] = acc;
             acc += t;
         }
@@ -1296,7 +1304,7 @@ __global__ __launch_bounds__(kSlots) __attribute__((amdgpu_waves_per_eu(6))) voi
 void launch_ordered_scatter(const Dims& d, const GeomArena& g, const ImageArena& im,
                             const BinArena& b, hipStream_t s) {
     if (d.P == 0 || d.B == 0) return;
-    const size_t lds = (size_t)(d.gx + d.gy) * 4 * 8 + (size_t)d.T * 4;
+    const size_t lds = scatter_lds(d);
     static size_t attr = 0;
     if (lds > 65536 && attr < lds) {
         attr = lds;
@@ -1324,6 +1332,32 @@ void launch_ordered_scatter(const Dims& d, const GeomArena& g, const ImageArena&
     if (!ws) hipLaunchKernelGGL((k_ordered_scatter<0, false>), gr, bl, lds, s, d, g, im, b, xo);
     else if (tile_scan_in_scatter(d)) hipLaunchKernelGGL((k_ordered_scatter<0, true, true>), gr, bl, lds, s, d, g, im, b, xo);
     else hipLaunchKernelGGL((k_ordered_scatter<0, true>), gr, bl, lds, s, d, g, im, b, xo);
+}
+
+// Both requests grow with gx + gy, not only with T: a very elongated image within kMaxTiles (16 x
+// 80000: T = 5000, gx + gy = 5001 -> 180 KB for the scatter) asks for more than a workgroup can
+// have, the launch fails and the render would walk an unwritten point_list.  The entry points
+// refuse such a grid before anything is launched.
+bool binning_lds_fits(const Dims& d, size_t* need, size_t* limit) {
+    static size_t lim = 0, stat_count = 0, stat_scatter = 0;
+    if (lim == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+            v = 65536;
+        hipFuncAttributes fa;
+        for (const void* f : {(const void*)k_chunk_count<true>, (const void*)k_chunk_count<false>})
+            if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat_count = std::max(stat_count, (size_t)fa.sharedSizeBytes);
+        for (const void* f : {(const void*)k_ordered_scatter<0, true>, (const void*)k_ordered_scatter<0, true, true>,
+                              (const void*)k_ordered_scatter<0, false>})
+            if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat_scatter = std::max(stat_scatter, (size_t)fa.sharedSizeBytes);
+        (void)hipGetLastError();
+        lim = (size_t)v;
+    }
+    const size_t n = std::max(chunk_count_lds(d) + stat_count, scatter_lds(d) + stat_scatter);
+    if (need) *need = n;
+    if (limit) *limit = lim;
+    return n <= lim;
 }
 
 // ---------------------------------------------------------------- 6. strip work list

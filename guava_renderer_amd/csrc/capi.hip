@@ -81,6 +81,18 @@ constexpr uint32_t kForwardBatchKnown = kNumericsKnown | GSR_FORWARD_ONLY;
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t ctrl_words(const Dims& d) { return (size_t)kCtrlWords + (size_t)kFsWords * d.B; }
 
+// the tile grid of a width x height image: empty when the binning can take it, else why not -- more
+// than kMaxTiles tiles, or a grid so elongated that the count / scatter kernels' LDS request
+// (growing with gx + gy) exceeds what one workgroup can have (binning_lds_fits)
+std::string grid_error(int width, int height) {
+    if ((int64_t)((width + 15) / 16) * ((height + 15) / 16) > kMaxTiles) return "image too large";
+    size_t need = 0, limit = 0;
+    if (!binning_lds_fits(make_dims(1, 1, width, height), &need, &limit))
+        return "image too elongated: the binning kernels need " + std::to_string(need) +
+               " bytes of LDS per workgroup for its tile grid, the device has " + std::to_string(limit);
+    return std::string();
+}
+
 template <typename T>
 inline T* take(char* base, size_t& off, size_t count) {
     off = align_up(off);
@@ -313,7 +325,7 @@ static int forward_single(gsr_alloc_fn geometryBuffer, gsr_alloc_fn binningBuffe
     if (P < 0 || width <= 0 || height <= 0) return fail(GSR_ERR_ARG, "bad P/width/height");
     if (numerics & ~kNumericsKnown) return fail(GSR_ERR_ARG, "unknown numerics flags");
     if (P >= kMaxGaussians) return fail(GSR_ERR_ARG, "P must be < 2^24");
-    if ((int64_t)((width + 15) / 16) * ((height + 15) / 16) > kMaxTiles) return fail(GSR_ERR_ARG, "image too large");
+    if (const std::string ge = grid_error(width, height); !ge.empty()) return fail(GSR_ERR_ARG, ge);
     const Dims d = make_dims(1, P, width, height);
     GeomArena g;
     ImageArena im;
@@ -597,7 +609,7 @@ static int forward_batch_impl(int B, int P, int width, int height, const float* 
     }
     if (B <= 0 || P <= 0 || width <= 0 || height <= 0 || !workspace || !tanfov)
         return fail(GSR_ERR_ARG, "bad batch arguments");
-    if ((int64_t)((width + 15) / 16) * ((height + 15) / 16) > kMaxTiles) return fail(GSR_ERR_ARG, "image too large");
+    if (const std::string ge = grid_error(width, height); !ge.empty()) return fail(GSR_ERR_ARG, ge);
     if (B > kMaxFrames) return fail(GSR_ERR_ARG, "too many frames per batch");
     if (P >= kMaxGaussians) return fail(GSR_ERR_ARG, "P must be < 2^24");
     if (!colors) return fail(GSR_ERR_NO_COLORS, "For non-RGB, provide precomputed Gaussian colors!");
@@ -881,8 +893,8 @@ int gsr_refine_backward_image(int B, int P, int width, int height, char* workspa
     if (B <= 0 || P <= 0 || width <= 0 || height <= 0 || !workspace)
         return fail(GSR_ERR_ARG, "gsr_refine_backward_image: bad batch arguments");
     if (B > kMaxFrames) return fail(GSR_ERR_ARG, "gsr_refine_backward_image: too many frames per batch");
-    if ((int64_t)((width + 15) / 16) * ((height + 15) / 16) > kMaxTiles)
-        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: image too large");
+    if (const std::string ge = grid_error(width, height); !ge.empty())
+        return fail(GSR_ERR_ARG, "gsr_refine_backward_image: " + ge);
     if (!desc->out_refine || !desc->dL_dout_refine || !desc->dL_dprepared)
         return fail(GSR_ERR_ARG, "gsr_refine_backward_image: null out_refine, dL_dout_refine or dL_dprepared");
     if (workspace_fwd_only(workspace))

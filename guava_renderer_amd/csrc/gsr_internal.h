@@ -334,6 +334,9 @@ void launch_strip_order(const Dims& d, const GeomArena& g, const ImageArena& im,
 void launch_strip_list_tile(const Dims& d, const ImageArena& im, uint32_t* out, hipStream_t s);
 void launch_ordered_scatter(const Dims& d, const GeomArena& g, const ImageArena& im,
                             const BinArena& b, hipStream_t s);
+// whether launch_chunk_count's and launch_ordered_scatter's LDS requests for this grid (dynamic plus
+// the kernels' static size) fit the device's per-workgroup limit; *need / *limit in bytes
+bool binning_lds_fits(const Dims& d, size_t* need = nullptr, size_t* limit = nullptr);
 void launch_render_fwd(const Dims& d, const Inputs& in, const GeomArena& g, const ImageArena& im,
                        const BinArena& b, const Outputs& o, bool exact, bool split, hipStream_t s);
 void launch_render_bwd(const Dims& d, const Inputs& in, const GeomArena& g, const ImageArena& im,

@@ -85,7 +85,10 @@ const char* gsr_last_error(void);
 /* Scratch sizes used by gsr_forward (the three resizer requests).  Unlike the reference's
  * GeometryState, the geometry arena also holds the per-frame depth sort and the (depth chunk x tile)
  * instance-count table, so it depends on the image size too.  Images are limited to 16384 tiles
- * (2048 x 2048 pixels). */
+ * (2048 x 2048 pixels), and to tile grids whose width + height (in 16-pixel tiles) keeps the binning
+ * kernels' per-workgroup LDS request within the device's limit (32 bytes per tile row and column
+ * plus 4 per tile: 16 x 16400 and 4096 x 1024 fit 160 KB, 16 x 80000 does not); the forward entry
+ * points return GSR_ERR_ARG for a larger image. */
 size_t gsr_geometry_bytes(int P, int width, int height);
 size_t gsr_image_bytes(int width, int height);
 size_t gsr_binning_bytes(int64_t R);

@@ -27,9 +27,41 @@ def layout_bytes(layout):
 
 # gsr_internal.h: control words, per-frame words behind them, depth-sort sizes
 CTRL_WORDS, FS_WORDS = 9216, 8
-CTRL_NUM_BIG = 3
-FS_NOT_KEY_MAX, FS_KEY_MAX, FS_VISIBLE = 0, 1, 2
+CTRL_R, CTRL_NUM_BIG, CTRL_NON_EMPTY, CTRL_QSTART = 0, 3, 6, 16
+FS_NOT_KEY_MAX, FS_KEY_MAX, FS_VISIBLE, FS_R, FS_RBASE, FS_NON_EMPTY = 0, 1, 2, 3, 4, 5
 TINY_BUCKET, SORT_SMALL_CAP, SORT_LARGE_CAP = 64, 2048, 8192
+SLOTS = 256                     # kSlots: Gaussians per ordered-scatter pass
+LPT_BUCKETS, STRIP_BUCKETS = 34, 129
+INDEX_MASK = (1 << 28) - 1      # kIndexMask: point_list entry -> Gaussian index; the strip mask sits above
+MAX_TILES = 16384               # kMaxTiles
+
+
+def tile_queue(t, gx):
+    """gsr_internal.h tile_queue: the XCD queue of tile t of a frame (4x4-tile blocks, shifted by 3 per
+    block row).  Scalars or arrays."""
+    tx, ty = t % gx, t // gx
+    return ((tx >> 2) + 3 * (ty >> 2)) & 7
+
+
+def strip_bucket(c):
+    """binning.hip strip_bucket: 4 buckets per octave of survivors, most first; 128 = none."""
+    c = int(c)
+    if c == 0:
+        return STRIP_BUCKETS - 1
+    e = c.bit_length() - 1
+    sub = (c >> (e - 2)) & 3 if e >= 2 else (c << (2 - e)) & 3
+    return 127 - (4 * e + sub)
+
+
+def lpt_bucket(c):
+    """k_tile_scan's work-list bucket of a tile with c list entries: clz(c), 33 = empty tile."""
+    c = int(c)
+    return 32 - c.bit_length() if c else LPT_BUCKETS - 1
+
+
+def chunk_rows(T):
+    """make_dims: depth-ordered Gaussians per count-table row."""
+    return (4 if T > 1024 else 1) * SLOTS
 
 
 def _nb(P):
@@ -46,7 +78,7 @@ def geom_layout(P, W, H, B=1):
     nblk = (P + 255) // 256
     T = ((W + 15) // 16) * ((H + 15) // 16)
     NB = _nb(P)
-    chunk = 1024 if T > 1024 else 256  # make_dims: count-table rows
+    chunk = chunk_rows(T)
     nchunk = (P + chunk - 1) // chunk
     n = B * P
     return _carve([("ctrl", np.uint32, CTRL_WORDS + FS_WORDS * B), ("depth", np.float32, n),
@@ -68,9 +100,43 @@ def image_layout(W, H):
                    ("strip_list", np.uint32, 4 * T), ("strip_hist", np.uint32, 8 * 129)])
 
 
+def batch_image_layout(W, H, B):
+    """carve_image of make_dims(B, ., W, H): every per-pixel and per-tile slab holds B frames back to
+    back; strip_hist is per frame 8 queues x 129 buckets (queue map 2: list offsets after
+    k_strip_qscan), strip_list_bwd the backward's own tile-major list."""
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    return _carve([("final_T", np.float32, B * W * H), ("n_contrib", np.uint32, B * W * H),
+                   ("ranges", np.uint32, 2 * B * T), ("tile_count", np.uint32, B * T),
+                   ("work_list", np.uint32, B * T), ("lpt_hist", np.uint32, B * LPT_BUCKETS),
+                   ("strip_cnt", np.uint32, 4 * B * T), ("strip_list", np.uint32, 4 * B * T),
+                   ("strip_hist", np.uint32, B * 8 * STRIP_BUCKETS), ("strip_list_bwd", np.uint32, 4 * B * T)])
+
+
 def bin_layout(R):
     n = max(R, 1)
     return _carve([("point_list", np.uint32, n)])
+
+
+def decode_batch_workspace(r, geom=True):
+    """The three arenas of a BatchRasterizer's workspace after a forward (carve_workspace in
+    csrc/capi.hip: geometry | image | binning) -> (geometry dict or None, image dict, bin dict).  The
+    bin arena is read as point_list[:R] with R the batch total of the control words."""
+    B, P, W, H = r.B, r.P, r.W, r.H
+    gl, il = geom_layout(P, W, H, B), batch_image_layout(W, H, B)
+    gsz, isz = layout_bytes(gl), layout_bytes(il)
+    ws = r.workspace
+    n4 = 4 * max(r.R_capacity, 1)
+    bsz = _align(_align(n4) + n4 if B == 1 else n4) + 256  # carve_bin: a quad-mask slab after the list at B = 1
+    assert gsz + isz + bsz + 256 == ws.numel(), ("the layouts are out of step with carve_workspace",
+                                                 gsz, isz, bsz, ws.numel())
+    R = int(np.frombuffer(ws[:4].cpu().numpy().tobytes(), np.uint32)[CTRL_R])
+    assert R <= r.R_capacity, (R, r.R_capacity)
+    gs = decode(ws[:gsz].cpu().numpy(), gl) if geom else None
+    im = decode(ws[gsz:gsz + isz].cpu().numpy(), il)
+    bn = decode(ws[gsz + isz:gsz + isz + 4 * max(R, 1)].cpu().numpy(), bin_layout(R))
+    bn["point_list"] = bn["point_list"][:R]
+    bn["R"] = R
+    return gs, im, bn
 
 
 def decode(buf_np, layout):

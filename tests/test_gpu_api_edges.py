@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_scene, torch_inputs, world_z_for_view_z as _world_z_for_view_z
+from helpers import gpu_forward, make_scene, torch_inputs, world_z_for_view_z as _world_z_for_view_z
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -283,3 +283,61 @@ def test_inference_path_equals_general_forward():
     assert col.grad_fn is not None
     col.sum().backward()
     assert means2D.grad is not None
+
+
+def test_elongated_grid_is_refused_before_any_launch():
+    """The count and scatter kernels' LDS requests grow with gx + gy: a 16 x 80000 image (T = 5000, within
+    kMaxTiles) would ask the scatter for 5001 * 32 + 4 * 5000 = 180032 bytes on top of its static LDS,
+    more than a workgroup can have.  All three entry points that take an image size refuse it with
+    GSR_ERR_ARG and say why, and nothing is launched: the poisoned workspace and outputs stay as they
+    were.  16 x 16400 (one tile wide) and 4096 x 1024 (kMaxTiles, the > 64 KB branch) are still
+    accepted and render."""
+    import ctypes
+    import oracle
+    from guava_renderer_amd import _lib, camera, scenes
+    from guava_renderer_amd._lib import GsrError
+    from guava_renderer_amd.batch import BatchRasterizer
+    from test_refine_backward import _desc
+    dev = torch.device("cuda:0")
+    P = 64
+    sc = scenes.random_cloud(P, seed=41)
+    t = lambda x: torch.tensor(np.ascontiguousarray(x), device=dev)  # noqa: E731
+
+    def args(B, W, H):
+        c = camera.camera(W, H)
+        return [t(sc[k]) for k in ("means3D", "colors", "opacities", "scales", "rotations")] + [
+            t(np.repeat(c["viewmatrix"].reshape(1, 16), B, 0)), t(np.repeat(c["projmatrix"].reshape(1, 16), B, 0)),
+            t(np.full((B, 2), c["tanfovx"], np.float32)), torch.zeros((B, 32), device=dev)], c
+    W, H = 16, 80000
+    assert ((W + 15) // 16) * ((H + 15) // 16) <= 16384
+    for B in (1, 2):
+        r = BatchRasterizer(B, P, W, H, R_capacity=1000, device=dev)
+        r.workspace[:-256].fill_(0xA5)  # (the sticky status words at the end stay zero)
+        r.out_color.fill_(7.0)
+        a, _ = args(B, W, H)
+        with pytest.raises(GsrError, match="elongated"):
+            r.forward(*a)
+        torch.cuda.synchronize()
+        assert (r.workspace[:-256] == 0xA5).all() and (r.out_color == 7.0).all()
+    L = _lib.load()
+    d = _desc()
+    assert L.gsr_refine_backward_image(2, P, W, H, 4096, 1000, ctypes.byref(d), None) == -1
+    assert b"elongated" in L.gsr_last_error()
+    d1 = make_scene("random", P, W, H, seed=41)
+    with pytest.raises(GsrError, match="elongated"):
+        gpu_forward(d1)
+    torch.cuda.synchronize()
+    # still accepted: the oracle's frame, bit for bit
+    for W, H in ((16, 16400), (4096, 1024)):
+        r = BatchRasterizer(2, P, W, H, R_capacity=200000, device=dev)
+        a, c = args(2, W, H)
+        col, inv, radii = r.forward(*a)
+        torch.cuda.synchronize()
+        assert not r.status()[1]
+        o_col, o_radii, _, _ = oracle.forward(sc["means3D"], sc["colors"], sc["opacities"], sc["scales"], sc["rotations"],
+                                              None, c["viewmatrix"], c["projmatrix"], W, H, c["tanfovx"], c["tanfovy"],
+                                              np.zeros(32, np.float32))
+        assert (o_radii > 0).sum() > P // 2
+        for f in range(2):
+            np.testing.assert_array_equal(radii[f].cpu().numpy(), o_radii)
+            np.testing.assert_array_equal(col[f].cpu().numpy(), o_col)

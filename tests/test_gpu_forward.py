@@ -8,6 +8,7 @@ colours within 1e-4 L_inf except on the rare pixels where an alpha threshold fli
 import numpy as np
 import pytest
 
+import helpers
 from helpers import gpu_forward, make_scene, oracle_forward
 
 pytestmark = pytest.mark.gpu
@@ -173,17 +174,11 @@ def test_strip_work_list():
     lst = gs["strip_list"][:n]
     assert sorted(lst.tolist()) == sorted((4 * nonempty[:, None] + np.arange(4)).reshape(-1).tolist())
 
-    def bucket(c):
-        if c == 0:
-            return 128
-        e = int(c).bit_length() - 1
-        sub = (c >> (e - 2)) & 3 if e >= 2 else (c << (2 - e)) & 3
-        return 127 - (4 * e + sub)
     groups = lst.reshape(-1, 4)
     assert (groups >> 2 == (groups[:, :1] >> 2)).all() and ((groups & 3) == np.arange(4)).all()
     # one frame: one longest-first list (batches of 2+ frames use per-XCD segments, each
     # longest-first: queue_item map 2; every batch test's bit-exact frames cover that walk)
-    b = [bucket(int(cnt[x >> 2].max())) for x in groups[:, 0]]
+    b = [helpers.strip_bucket(int(cnt[x >> 2].max())) for x in groups[:, 0]]
     assert all(b[i] <= b[i + 1] for i in range(len(b) - 1))
 
 

@@ -132,12 +132,7 @@ def _batch_image_state(r):
     the head of the batch workspace's image arena (carve_image in csrc/capi.hip)."""
     B, W, H = r.B, r.W, r.H
     T = ((W + 15) // 16) * ((H + 15) // 16)
-    lay = helpers._carve([("final_T", np.float32, B * W * H), ("n_contrib", np.uint32, B * W * H),
-                          ("ranges", np.uint32, 2 * B * T), ("tile_count", np.uint32, B * T),
-                          ("work_list", np.uint32, B * T), ("lpt_hist", np.uint32, B * 34),
-                          ("strip_cnt", np.uint32, 4 * B * T)])
-    gsz = helpers.layout_bytes(helpers.geom_layout(r.P, W, H, B))
-    st = helpers.decode(r.workspace[gsz:gsz + helpers.layout_bytes(lay)].cpu().numpy(), lay)
+    _, st, _ = helpers.decode_batch_workspace(r, geom=False)
     return (st["final_T"].reshape(B, H, W), st["n_contrib"].reshape(B, H, W), st["ranges"].reshape(B * T, 2),
             st["strip_cnt"].reshape(B * T, 4))
 
