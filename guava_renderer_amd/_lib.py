@@ -14,7 +14,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_forward_async_bound", "gsr_forward_async",
            "gsr_backward", "gsr_backward_ex", "gsr_batch_workspace_bytes", "gsr_forward_batch",
            "gsr_backward_batch", "gsr_backward_batch_shared", "gsr_batch_status", "gsr_profile_enable", "gsr_profile_read",
-           "gsr_render_counters", "gsr_render_timeline", "gsr_forward_batch_refine",
+           "gsr_render_counters", "gsr_render_timeline", "gsr_forward_batch_refine", "gsr_render_variant",
            "gsr_refine_prepare", "gsr_batch_status_offset", "gsr_frames_to8b",
            "gsr_refine_backward_scratch_bytes", "gsr_refine_backward_image", "gsr_refine_backward_rows",
            "gsr_stream_create_cu_mask", "gsr_stream_destroy", "gsr_set_render_stream",
@@ -22,6 +22,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_lbs_workspace_bytes", "gsr_lbs", "gsr_lbs_sp", "gsr_blend_joints", "gsr_blend_joints_sp",
            "gsr_lbs_tiled_floats", "gsr_lbs_tile_bases",
            "gsr_scratch_geometry", "gsr_scratch_binning", "gsr_scratch_image", "gsr_forward_batch_deformed",
+           "gsr_forward_batch_deformed_refine",
            "gsr_splice_head",
            "gsr_pack_rows", "gsr_deform_gaussians", "gsr_ehm_workspace_bytes", "gsr_ehm_forward",
            "gsr_deform_gaussians_backward", "gsr_backward_batch_deformed",
@@ -37,6 +38,9 @@ NUMERICS_FAST_EXP = 1
 NUMERICS_SPLIT_BF16 = 2
 # same flag word, batched forward only: no backward will read the workspace (include/gsr.h)
 FORWARD_ONLY = 0x100
+# gsr_render_variant's answers (include/gsr.h GSR_RENDER_*), by value
+RENDER_VARIANTS = ("strip", "strip_fwd", "split_frame", "split_shared", "split_shared_fwd", "refine", "refine_fwd",
+                   "quad", "quad_refine", "half", "half_split", "stats", "timeline", "quad_timeline")
 
 
 def numerics(fast_exp=False, split_bf16=False):
@@ -209,6 +213,11 @@ def load(path=None):
     L.gsr_forward_batch_deformed.argtypes = [_i, _i, _i, ctypes.POINTER(DeformInputs), _vp, _i64, _vp, _i64, _f,
                                              _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _u32, _vp]
     L.gsr_forward_batch_deformed.restype = _i
+    L.gsr_forward_batch_deformed_refine.argtypes = list(L.gsr_forward_batch_deformed.argtypes[:-2]) + [
+        ctypes.POINTER(RefineEpilogue), _u32, _vp]
+    L.gsr_forward_batch_deformed_refine.restype = _i
+    L.gsr_render_variant.argtypes = [_i, _u32, _i]
+    L.gsr_render_variant.restype = _i
     L.gsr_refine_prepare.argtypes = [_i, _vp, _vp, _i, _i, _vp, _vp]
     L.gsr_refine_prepare.restype = _i
     L.gsr_refine_backward_scratch_bytes.argtypes = [_i, _i, _i, _i, _i]
@@ -303,6 +312,14 @@ def load(path=None):
     L.gsr_uv_regularizers.restype = _i
     _lib = L
     return L
+
+
+def render_variant(B, numerics=0, refine=False):
+    """Name (RENDER_VARIANTS) of the compositing kernel a batched forward of B frames takes with this
+    flag word (numerics bits | FORWARD_ONLY), with or without a refiner head: gsr_render_variant, the
+    launcher's own selection."""
+    return RENDER_VARIANTS[check(load().gsr_render_variant(int(B), int(numerics), int(bool(refine))),
+                                 "gsr_render_variant")]
 
 
 def check(rc, what):

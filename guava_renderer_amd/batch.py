@@ -198,12 +198,14 @@ class BatchRasterizer:
         return self.out_color, self.out_invdepth, self.radii
 
     def forward_deformed(self, deformer, verts, vert_transforms, viewmatrices, projmatrices, tanfov, backgrounds,
-                         scale_modifier=1.0, antialiasing=False, numerics=None):
+                         scale_modifier=1.0, antialiasing=False, numerics=None, refine=None):
         """The avatar pipeline's fused forward (include/gsr_deform.h gsr_forward_batch_deformed): the
         B frames of `deformer` (deform.GaussianDeformer) on the deformed mesh verts [B,V,3] /
         vert_transforms [B,V,4,4], rendered without materialising the deformed Gaussians (their
         assembly feeds the projection in registers).  Same images as deformer.forward() + forward();
-        forward-only (a backward() after it raises)."""
+        forward-only (a backward() after it raises).  refine: optional RefineHead, as forward()'s
+        (gsr_forward_batch_deformed_refine): its output is refine.out and only
+        out_color[:, :refine.keep_channels] is written."""
         self.poll()
         nm = self.numerics if numerics is None else int(numerics)
         self._fwd_only = True
@@ -227,11 +229,21 @@ class BatchRasterizer:
                                dfm.faces.data_ptr(), dfm.v_rot.data_ptr(), 0, dfm.v_scale.data_ptr(), 0,
                                dfm.bind.data_ptr(), dfm.bary.data_ptr(), dfm.u_local.data_ptr(), 0,
                                dfm.u_rot.data_ptr(), 0, dfm.u_scale.data_ptr(), 0, dfm.bad.data_ptr())
-        _lib.check(self.L.gsr_forward_batch_deformed(
-            B, self.W, self.H, ctypes.byref(di), head[6], head[7], head[8], head[9], float(scale_modifier),
-            v, pm, tf, bg, bs, self.workspace.data_ptr(), self.R_capacity, self.out_color.data_ptr(),
-            self.out_invdepth.data_ptr(), self.radii.data_ptr(), int(bool(antialiasing)), nm, self._stream()),
-            "gsr_forward_batch_deformed")
+        args = (B, self.W, self.H, ctypes.byref(di), head[6], head[7], head[8], head[9], float(scale_modifier),
+                v, pm, tf, bg, bs, self.workspace.data_ptr(), self.R_capacity, self.out_color.data_ptr(),
+                self.out_invdepth.data_ptr(), self.radii.data_ptr(), int(bool(antialiasing)))
+        if refine is None:
+            _lib.check(self.L.gsr_forward_batch_deformed(*args, nm, self._stream()), "gsr_forward_batch_deformed")
+        else:
+            # the pre-contracted rows, features and backgrounds alike (as forward(refine=head))
+            pc = refine.prepare(keep[1], self._stream())
+            pb = refine.prepare(keep[8].reshape(-1, C), self._stream(), cache=False)
+            args = list(args)
+            args[4] = pc.data_ptr()
+            args[12] = pb.data_ptr()
+            ep = refine.epilogue(B, self.H, self.W)
+            _lib.check(self.L.gsr_forward_batch_deformed_refine(*args, ctypes.byref(ep), nm, self._stream()),
+                       "gsr_forward_batch_deformed_refine")
         del keep, vb, vt
         self._after_forward()
         return self.out_color, self.out_invdepth, self.radii

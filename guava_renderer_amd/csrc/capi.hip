@@ -687,12 +687,32 @@ int gsr_forward_batch_refine(int B, int P, int width, int height, const float* m
                               (hipStream_t)stream);
 }
 
+int gsr_render_variant(int B, uint32_t numerics, int has_refine) {
+    if (B < 1 || (numerics & ~kForwardBatchKnown)) return fail(GSR_ERR_ARG, "gsr_render_variant: B >= 1, known flags");
+    // (a B = 1 workspace carries the quad-mask slab: carve_workspace)
+    return select_render_variant(B, split_bf16(numerics), (numerics & GSR_FORWARD_ONLY) != 0, has_refine != 0, true,
+                                 g_render_counters != nullptr, g_timeline != nullptr, B == 1);
+}
+
 int gsr_forward_batch_deformed(int B, int width, int height, const GsrDeformInputs* dg, const float* colors,
                                int64_t colors_stride, const float* opacities, int64_t opac_stride,
                                float scale_modifier, const float* viewmatrices, const float* projmatrices,
                                const float* tanfov, const float* backgrounds, int64_t bg_stride,
                                char* workspace, int64_t R_capacity, float* out_color, float* out_invdepth,
                                int* radii, int antialiasing, uint32_t numerics, void* stream) {
+    return gsr_forward_batch_deformed_refine(B, width, height, dg, colors, colors_stride, opacities, opac_stride,
+                                             scale_modifier, viewmatrices, projmatrices, tanfov, backgrounds,
+                                             bg_stride, workspace, R_capacity, out_color, out_invdepth, radii,
+                                             antialiasing, nullptr, numerics, stream);
+}
+
+int gsr_forward_batch_deformed_refine(int B, int width, int height, const GsrDeformInputs* dg, const float* colors,
+                                      int64_t colors_stride, const float* opacities, int64_t opac_stride,
+                                      float scale_modifier, const float* viewmatrices, const float* projmatrices,
+                                      const float* tanfov, const float* backgrounds, int64_t bg_stride,
+                                      char* workspace, int64_t R_capacity, float* out_color, float* out_invdepth,
+                                      int* radii, int antialiasing, const gsr_refine_epilogue* refine,
+                                      uint32_t numerics, void* stream) {
     if (!dg || dg->V < 0 || dg->N < 0 || dg->F < 0 || dg->V + dg->N == 0 || !dg->verts)
         return fail(GSR_ERR_ARG, "gsr_forward_batch_deformed: bad deform inputs");
     if (dg->V > 0 && (!dg->vert_transforms || !dg->vtx_rotations || !dg->vtx_scales))
@@ -708,7 +728,7 @@ int gsr_forward_batch_deformed(int B, int width, int height, const GsrDeformInpu
     return forward_batch_impl(B, dg->V + dg->N, width, height, nullptr, 0, colors, colors_stride, opacities,
                               opac_stride, nullptr, 0, nullptr, 0, scale_modifier, viewmatrices, projmatrices,
                               tanfov, backgrounds, bg_stride, workspace, R_capacity, out_color, out_invdepth, radii,
-                              antialiasing, nullptr, numerics | GSR_FORWARD_ONLY, dg, (hipStream_t)stream);
+                              antialiasing, refine, numerics | GSR_FORWARD_ONLY, dg, (hipStream_t)stream);
 }
 
 int gsr_refine_prepare(int n, const float* rows, const float* weight, int n_out, int keep_channels,

@@ -248,6 +248,11 @@ int persistent_grid(int per_cu);
 // whether a forward of these dims / numerics / outputs composites on the single-frame quad kernel
 // (the only reader of the binning arena's quad masks): otherwise no mask is carved or computed
 bool render_uses_quad(const Dims& d, bool split, const Outputs& o);
+// The compositing kernel of a forward (include/gsr.h GSR_RENDER_*), from host-side facts alone: the
+// one choice launch_render_fwd, render_uses_quad and gsr_render_variant all make.  shared_colors: one
+// feature table for the batch (frame stride 0); qmask: the binning arena carries quad masks.
+int select_render_variant(int B, bool split, bool fwd_only, bool refine, bool shared_colors, bool stats,
+                          bool timeline, bool qmask);
 // persistent grid of a launch on stream s: the CUs that stream may use (a CU-masked stream made by
 // gsr_stream_create_cu_mask) times per_cu
 int persistent_grid_on(hipStream_t s, int per_cu);

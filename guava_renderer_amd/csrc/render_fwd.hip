@@ -27,6 +27,7 @@
 // Roofline: per frame the kernel must read 156 B per visible Gaussian (features + 2D attributes)
 // and write 140 B per pixel (32 channels, inverse depth, final_T, n_contrib); 132 B forward-only
 // (FWD: final_T and n_contrib are the backward's and are not written).
+#include "../../include/gsr.h"
 #include "gsr_cull.h"
 #include "gsr_internal.h"
 
@@ -278,6 +279,48 @@ __device__ __forceinline__ void fill_tile(const Dims& d, const ImageArena& im, c
     if (o.out_invdepth) *reinterpret_cast<uint4x*>(o.out_invdepth + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
 }
 
+// The empty tile of a refiner-head forward (fill_tile's conditions, out_refine 16-byte aligned as
+// well): channels [0, keep) of out_color are the background, out_refine[o] is the head's output on
+// the background alone, leaky(bg[keep + o] + bias[o]) -- the operations of store_strip<true, true>
+// on the same values, so the same bits -- and out_color's channels from keep on are not written.
+template <bool FWD = false>
+__device__ __forceinline__ void fill_tile_refine(const Dims& d, const ImageArena& im, const Outputs& o,
+                                                 const float* bg, int b, int tx, int ty, int lane) {
+    const int64_t HW = (int64_t)d.H * d.W;
+    const int off = (ty * GSR_BY + lane / 4) * d.W + tx * GSR_BX + 4 * (lane % 4);  // first pixel, in floats
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        o.out_color + (int64_t)b * GSR_C * HW, 0, (int)((int64_t)GSR_C * HW * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+        o.out_refine + (int64_t)b * o.n_out * HW, 0, (int)((int64_t)o.n_out * HW * 4), 0x00020000);
+    for (int c = 0; c < o.keep; c++) {
+        const unsigned v = __float_as_uint(bg[c]);
+        __builtin_amdgcn_raw_buffer_store_b128((uint4x){v, v, v, v}, rs, off * 4, c * (int)HW * 4, 0);
+    }
+    for (int oc = 0; oc < o.n_out; oc++) {
+        const float bias = o.rb ? o.rb[oc] : 0.0f;
+        float y = bg[o.keep + oc] + bias;
+        y = y >= 0.0f ? y : y * o.slope;
+        const unsigned v = __float_as_uint(y);
+        __builtin_amdgcn_raw_buffer_store_b128((uint4x){v, v, v, v}, rr, off * 4, oc * (int)HW * 4, 0);
+    }
+    if (!FWD) {
+        const unsigned one = __float_as_uint(1.0f);
+        *reinterpret_cast<uint4x*>(im.final_T + b * HW + off) = (uint4x){one, one, one, one};
+        *reinterpret_cast<uint4x*>(im.n_contrib + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
+    }
+    if (o.out_invdepth) *reinterpret_cast<uint4x*>(o.out_invdepth + b * HW + off) = (uint4x){0u, 0u, 0u, 0u};
+}
+
+// whether an empty tile t takes the 16-byte fill: W a multiple of 4, the outputs 16-byte aligned
+// (out_refine too where the head writes it) and the tile wholly inside the image
+template <bool REFINE>
+__device__ __forceinline__ bool tile_fill_ok(const Dims& d, const Outputs& o, int t) {
+    uintptr_t ptrs = reinterpret_cast<uintptr_t>(o.out_color) | reinterpret_cast<uintptr_t>(o.out_invdepth);
+    if (REFINE) ptrs |= reinterpret_cast<uintptr_t>(o.out_refine);
+    return (d.W & 3) == 0 && (ptrs & 15u) == 0 && (t % d.gx + 1) * GSR_BX <= d.W &&
+           (t / d.gx + 1) * GSR_BY <= d.H;
+}
+
 // gsr_refine_prepare: rows [f_0..f_{keep-1}, W.f (n_out values), 0...] of 32 floats.
 __global__ __launch_bounds__(256) void k_refine_prepare(int n, const float* __restrict__ in,
                                                         const float* __restrict__ w, int n_out,
@@ -357,8 +400,8 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
     }
     static_assert(!HALF || (!STATS && !TL && !REFINE && ABL == 0), "half-strip waves: production kernel only");
     static_assert(NSLOT == 3 || NSLOT == 5, "three or five pipeline slots");
-    static_assert(!FWD || (!STATS && !TL && !REFINE && !HALF && ABL == 0 && NSLOT == 3 && SPLIT != 1),
-                  "forward-only: the production 3-slot batched kernel only");
+    static_assert(!FWD || (!STATS && !TL && !HALF && ABL == 0 && NSLOT == 3 && SPLIT != 1),
+                  "forward-only: the production 3-slot batched kernels (plain and refiner head) only");
     const uint32_t ne = g.ctrl[kCtrlNonEmpty];
     // HALF: every strip is two work items (one wave per 32-pixel half, the strip's rows 0-3 / 4-7)
     const uint32_t nstrip = (HALF ? 2u : 1u) * (uint32_t)kStrips * ne;
@@ -389,11 +432,9 @@ __device__ __forceinline__ void render_fwd_body(const Dims& d, const Inputs& in,
             const int t = tile_g - b * d.T;
             const floatx16 unused = {};
             if (ABL == 8) {  /* timing ablation: no empty-tile stores */
-            } else if (!REFINE && (d.W & 3) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(o.out_color) | reinterpret_cast<uintptr_t>(o.out_invdepth)) &
-                        15u) == 0 &&
-                       (t % d.gx + 1) * GSR_BX <= d.W && (t / d.gx + 1) * GSR_BY <= d.H) {
-                fill_tile<FWD>(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
+            } else if (tile_fill_ok<REFINE>(d, o, t)) {
+                if constexpr (REFINE) fill_tile_refine<FWD>(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
+                else fill_tile<FWD>(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
             } else {
                 for (int sp = 0; sp < kStrips; sp++) {
                     int ex0, ey0;
@@ -772,11 +813,17 @@ void k_render_fwd_ablate(Dims d, Inputs in, GeomArena g, ImageArena im, BinArena
 
 // The refiner-head variant: the epilogue's extra stores would raise the register count past the
 // 4-waves-per-SIMD budget of the blend loop; pin the budget (the few extra live values of the
-// epilogue spill instead).
-template <bool EXACT>
-__global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(4))) void k_render_fwd_refine(
+// epilogue spill instead).  FWD (GSR_FORWARD_ONLY with the head): the blend loop of the forward-only
+// kernel -- no last contributor, no final_T / n_contrib stores -- under the head's epilogue, at
+// GSR_REFINE_FWD_WPE waves per SIMD.
+#ifndef GSR_REFINE_FWD_WPE
+#define GSR_REFINE_FWD_WPE 4  // (5: 28 registers spilled, three reloaded inside the loop; 1471 against 1310 us)
+#endif
+template <bool EXACT, bool FWD = false>
+__global__ __launch_bounds__(GSR_TILE_PIX)
+__attribute__((amdgpu_waves_per_eu(FWD ? GSR_REFINE_FWD_WPE : 4))) void k_render_fwd_refine(
     Dims d, Inputs in, GeomArena g, ImageArena im, BinArena bn, Outputs o) {
-    render_fwd_body<EXACT, false, false, true>(d, in, g, im, bn, o);
+    render_fwd_body<EXACT, false, false, true, 0, 0, 3, false, FWD>(d, in, g, im, bn, o);
 }
 
 // ---------------------------------------------------------------- one frame: quad waves
@@ -826,7 +873,8 @@ constexpr uint32_t kQNull = 0x07FFFFFFu;  // the null Gaussian: record / feature
 
 // TL (gsr_render_timeline): per quad item, (start, end) in 100 MHz ticks, steps | refills << 16, list
 // entries walked
-template <bool EXACT, bool TL = false>
+// REFINE: the refiner head's epilogue (store_strip's, per lane: the lane groups hold different channels)
+template <bool EXACT, bool TL = false, bool REFINE = false>
 __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(GSR_QUAD_WPE))) void k_render_quad(
     Dims d, Inputs in, GeomArena g, ImageArena im, BinArena bn, Outputs o, int prio_n) {
     if (g.ctrl[kCtrlOverflow]) {
@@ -870,18 +918,16 @@ __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(GS
             const int tile_g = (int)im.work_list[ne + (item - nquad)];
             const int b = tile_g / d.T;
             const int t = tile_g - b * d.T;
-            if ((d.W & 3) == 0 &&
-                ((reinterpret_cast<uintptr_t>(o.out_color) | reinterpret_cast<uintptr_t>(o.out_invdepth)) & 15u) ==
-                    0 &&
-                (t % d.gx + 1) * GSR_BX <= d.W && (t / d.gx + 1) * GSR_BY <= d.H) {
-                fill_tile(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
+            if (tile_fill_ok<REFINE>(d, o, t)) {
+                if constexpr (REFINE) fill_tile_refine(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
+                else fill_tile(d, im, o, in.bg + in.s_bg * b, b, t % d.gx, t / d.gx, lane);
             } else {
                 const floatx16 unused = {};
                 for (int sp = 0; sp < kStrips; sp++) {
                     int ex0, ey0;
                     strip_origin(t % d.gx, t / d.gx, sp, ex0, ey0);
-                    store_strip<true, false>(d, im, o, in.bg + in.s_bg * b, b, ex0, ey0, lane, unused, unused, 1.0f,
-                                             0.f, 0u);
+                    store_strip<true, REFINE>(d, im, o, in.bg + in.s_bg * b, b, ex0, ey0, lane, unused, unused, 1.0f,
+                                              0.f, 0u);
                 }
             }
             continue;
@@ -1143,13 +1189,43 @@ __global__ __launch_bounds__(GSR_TILE_PIX) __attribute__((amdgpu_waves_per_eu(GS
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             o.out_color + (int64_t)b * GSR_C * HW, 0, (int)((int64_t)GSR_C * HW * 4), 0x00020000);
         const int vo = inside ? (int)(pix * 4) : 0x7FFFFFF0;
+        if constexpr (!REFINE) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int c0_ = 4 * qq + r, c1_ = 16 + 4 * qq + r;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaf(T, bgp[c0_], qa0[r])), rs, vo,
-                                                  c0_ * (int)HW * 4, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaf(T, bgp[c1_], qa1[r])), rs, vo,
-                                                  c1_ * (int)HW * 4, 0);
+            for (int r = 0; r < 4; r++) {
+                const int c0_ = 4 * qq + r, c1_ = 16 + 4 * qq + r;
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaf(T, bgp[c0_], qa0[r])), rs, vo,
+                                                      c0_ * (int)HW * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaf(T, bgp[c1_], qa1[r])), rs, vo,
+                                                      c1_ * (int)HW * 4, 0);
+            }
+        } else {
+            // store_strip's refiner epilogue per lane, branch-free: a channel below keep goes to
+            // out_color, one in [keep, keep + n_out) gets the bias and the leaky ReLU and goes to
+            // out_refine, and the output a channel does not belong to gets an offset past its buffer
+            // (dropped by the range check).  The bias through a resource of n_out words (none
+            // without a bias): a channel outside the head reads 0.
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+                o.out_refine + (int64_t)b * o.n_out * HW, 0, (int)((int64_t)o.n_out * HW * 4), 0x00020000);
+            const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)o.rb, 0, o.rb ? o.n_out * 4 : 0, 0x00020000);
+            auto put = [&](int c, float x) {
+                const int oc = c - o.keep;
+                const bool col = c < o.keep, ref = oc >= 0 && oc < o.n_out;
+                const float bias = __uint_as_float(
+                    __builtin_amdgcn_raw_buffer_load_b32(brs, ref ? oc * 4 : 0x7FFFFFF0, 0, 0));
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rs,
+                                                      (col && inside) ? vo + c * (int)HW * 4 : 0x7FFFFFF0, 0, 0);
+                float y = x + bias;
+                y = y >= 0.0f ? y : y * o.slope;  // F.leaky_relu_(x, 0.2)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), rr,
+                                                      (ref && inside) ? vo + oc * (int)HW * 4 : 0x7FFFFFF0, 0, 0);
+            };
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int c0_ = 4 * qq + r, c1_ = 16 + 4 * qq + r;
+                put(c0_, fmaf(T, bgp[c0_], qa0[r]));
+                put(c1_, fmaf(T, bgp[c1_], qa1[r]));
+            }
         }
     }
 }
@@ -1160,8 +1236,33 @@ static bool quad_mode_on() {
     return v;
 }
 
+// GSR_RENDER_HALF=0: single-frame launches on the throughput kernel (A/B)
+static bool half_mode_on() {
+    static const bool v = tune_env("GSR_RENDER_HALF", 1) != 0;
+    return v;
+}
+
+// The one choice of compositing kernel (gsr_internal.h): instrumented kernels first, then the
+// refiner head, the single-frame kernels, split-bf16 and the plain strip kernel.
+int select_render_variant(int B, bool split, bool fwd_only, bool refine, bool shared_colors, bool stats,
+                          bool timeline, bool qmask) {
+    const bool quad = B == 1 && quad_mode_on() && !split && qmask;
+    if (stats) return GSR_RENDER_STATS;
+    if (timeline) return quad && !refine ? GSR_RENDER_QUAD_TIMELINE : GSR_RENDER_TIMELINE;
+    // (the head composites f32 whatever the split flag says: a split single frame takes the strip kernel)
+    if (refine) return quad ? GSR_RENDER_QUAD_REFINE : fwd_only ? GSR_RENDER_REFINE_FWD : GSR_RENDER_REFINE;
+    if (quad) return GSR_RENDER_QUAD;
+    if (B == 1 && half_mode_on()) return split ? GSR_RENDER_HALF_SPLIT : GSR_RENDER_HALF;
+    if (split && shared_colors) return fwd_only ? GSR_RENDER_SPLIT_SHARED_FWD : GSR_RENDER_SPLIT_SHARED;
+    if (split) return GSR_RENDER_SPLIT_FRAME;
+    return fwd_only ? GSR_RENDER_STRIP_FWD : GSR_RENDER_STRIP;
+}
+
+// (asked before the binning arena is carved: a B = 1 arena carries the mask slab whenever this says so)
 bool render_uses_quad(const Dims& d, bool split, const Outputs& o) {
-    return d.B == 1 && quad_mode_on() && !split && !o.stats && !o.out_refine;
+    const int v = select_render_variant(d.B, split, false, o.out_refine != nullptr, true, o.stats != nullptr,
+                                        o.timeline != nullptr, true);
+    return v == GSR_RENDER_QUAD || v == GSR_RENDER_QUAD_REFINE || v == GSR_RENDER_QUAD_TIMELINE;
 }
 
 void launch_render_fwd(const Dims& d, const Inputs& in_, const GeomArena& g, const ImageArena& im,
@@ -1176,10 +1277,7 @@ void launch_render_fwd(const Dims& d, const Inputs& in_, const GeomArena& g, con
     // 6-frame training batch, where fewer strips per wave leave a longer tail).
     static const int wg_env = tune_env("GSR_RENDER_WG_PER_CU", 0);
     const int wg_per_cu = wg_env > 0 ? wg_env : (d.B >= 16 ? GSR_RENDER_WPE : 4);
-    // GSR_RENDER_HALF=0: single-frame launches on the throughput kernel (A/B); GSR_RENDER_HALF_WG: WGs per CU
-    static const bool half_mode = tune_env("GSR_RENDER_HALF", 1) != 0;
-    // (GSR_RENDER_QUAD_WG: quad-kernel workgroups per CU)
-    const bool quad_mode = quad_mode_on();
+    // (GSR_RENDER_QUAD_WG / GSR_RENDER_HALF_WG: quad- and half-strip-kernel workgroups per CU)
     static const int quad_wg = tune_env("GSR_RENDER_QUAD_WG", GSR_QUAD_WPE);
     static const int half_wg = tune_env("GSR_RENDER_HALF_WG", GSR_HALF_WPE);
     const int grid = min((nwaves + 3) / 4, persistent_grid_on(s, wg_per_cu));
@@ -1199,26 +1297,46 @@ void launch_render_fwd(const Dims& d, const Inputs& in_, const GeomArena& g, con
         if (exact) hipLaunchKernelGGL((k_render_fwd<true, __VA_ARGS__>), gr, bl, 0, s, d, in, g, im, b, o);   \
         else hipLaunchKernelGGL((k_render_fwd<false, __VA_ARGS__>), gr, bl, 0, s, d, in, g, im, b, o);        \
     }
-    if (o.stats) {
+    const dim3 gq(min((4 * nwaves + 3) / 4, persistent_grid(quad_wg)));  // quad kernels: 16 items per tile
+    switch (select_render_variant(d.B, split, in.fwd_only != 0, o.out_refine != nullptr, in.s_colors == 0,
+                                  o.stats != nullptr, o.timeline != nullptr, b.qmask != nullptr)) {
+    case GSR_RENDER_STATS:
         GSR_LAUNCH(0, true, false)
-    } else if (o.timeline && d.B == 1 && quad_mode && !split && b.qmask) {  // the quad kernel's own timeline
-        const dim3 gq(min((4 * nwaves + 3) / 4, persistent_grid(quad_wg)));
+        break;
+    case GSR_RENDER_QUAD_TIMELINE:  // the quad kernel's own timeline
         if (exact) hipLaunchKernelGGL((k_render_quad<true, true>), gq, bl, 0, s, d, in, g, im, b, o, 0);
         else hipLaunchKernelGGL((k_render_quad<false, true>), gq, bl, 0, s, d, in, g, im, b, o, 0);
-    } else if (o.timeline) {
+        break;
+    case GSR_RENDER_TIMELINE:
         GSR_LAUNCH(0, false, true)
-    } else if (o.out_refine) {  // (4-wave register budget: 4 workgroups per CU)
+        break;
+    case GSR_RENDER_REFINE: {  // (4-wave register budget: 4 workgroups per CU)
         const dim3 grf(min((nwaves + 3) / 4, persistent_grid(4)));
         if (exact) hipLaunchKernelGGL((k_render_fwd_refine<true>), grf, bl, 0, s, d, in, g, im, b, o);
         else hipLaunchKernelGGL((k_render_fwd_refine<false>), grf, bl, 0, s, d, in, g, im, b, o);
-    } else if (d.B == 1 && quad_mode && !split && b.qmask) {
+        break;
+    }
+    case GSR_RENDER_REFINE_FWD: {  // forward-only with the head: GSR_REFINE_FWD_WPE waves per SIMD
+        const int per_cu = GSR_REFINE_FWD_WPE > 4 && d.B < 16 ? 4 : GSR_REFINE_FWD_WPE;
+        const dim3 grf(min((nwaves + 3) / 4, persistent_grid(per_cu)));
+        if (exact) hipLaunchKernelGGL((k_render_fwd_refine<true, true>), grf, bl, 0, s, d, in, g, im, b, o);
+        else hipLaunchKernelGGL((k_render_fwd_refine<false, true>), grf, bl, 0, s, d, in, g, im, b, o);
+        break;
+    }
+    case GSR_RENDER_QUAD_REFINE:  // one frame with the head: quad waves, the head's epilogue per lane
+        if (exact) hipLaunchKernelGGL((k_render_quad<true, false, true>), gq, bl, 0, s, d, in, g, im, b, o, 0);
+        else hipLaunchKernelGGL((k_render_quad<false, false, true>), gq, bl, 0, s, d, in, g, im, b, o, 0);
+        break;
+    case GSR_RENDER_QUAD: {
         // one frame, quad waves walking their quad masks: the longest quads' chains are what count here
-        const dim3 gq(min((4 * nwaves + 3) / 4, persistent_grid(quad_wg)));
         // GSR_QUAD_PRIO: queue items per XCD that run at issue priority 1 (A/B)
         static const int prio_n = tune_env("GSR_QUAD_PRIO", 0);
         if (exact) hipLaunchKernelGGL((k_render_quad<true>), gq, bl, 0, s, d, in, g, im, b, o, prio_n);
         else hipLaunchKernelGGL((k_render_quad<false>), gq, bl, 0, s, d, in, g, im, b, o, prio_n);
-    } else if (d.B == 1 && half_mode) {
+        break;
+    }
+    case GSR_RENDER_HALF:
+    case GSR_RENDER_HALF_SPLIT: {
         // one frame, half-strip waves: a strip's two halves run in parallel, each lane one
         // (pixel, Gaussian) alpha per k-step -- the longest strip's time is what counts here
         const dim3 gl(min((2 * nwaves + 3) / 4, persistent_grid(half_wg)));
@@ -1229,19 +1347,26 @@ void launch_render_fwd(const Dims& d, const Inputs& in_, const GeomArena& g, con
             if (exact) hipLaunchKernelGGL((k_render_fwd<true, false, false, 0, 5, true>), gl, bl, 0, s, d, in, g, im, b, o);
             else hipLaunchKernelGGL((k_render_fwd<false, false, false, 0, 5, true>), gl, bl, 0, s, d, in, g, im, b, o);
         }
-    } else if (split && in.s_colors == 0) {  // one feature set for the batch: split it once
+        break;
+    }
+    case GSR_RENDER_SPLIT_SHARED:
+    case GSR_RENDER_SPLIT_SHARED_FWD:  // one feature set for the batch: split it once
         hipLaunchKernelGGL(k_split_features, dim3((d.P * GSR_C / 4 + 255) / 256), dim3(256), 0, s,
                            d.P * GSR_C / 4, reinterpret_cast<const float4*>(in.colors),
                            reinterpret_cast<uint4*>(g.fsplit));
         // forward-only (GSR_FORWARD_ONLY): the instantiation without the backward's per-pixel state
         if (in.fwd_only) GSR_LAUNCH(0, false, false, 2, GSR_BATCH_NSLOT, false, true)
         else GSR_LAUNCH(0, false, false, 2)
-    } else if (split) {
+        break;
+    case GSR_RENDER_SPLIT_FRAME:
         GSR_LAUNCH(0, false, false, 1)
-    } else if (in.fwd_only) {
+        break;
+    case GSR_RENDER_STRIP_FWD:
         GSR_LAUNCH(0, false, false, 0, GSR_BATCH_NSLOT, false, true)
-    } else {
+        break;
+    default:
         GSR_LAUNCH(0, false, false)
+        break;
     }
 #undef GSR_LAUNCH
 }

@@ -72,15 +72,51 @@ const char* gsr_last_error(void);
  * render_motion.py).  Preprocess then writes only what binning and compositing read (depth, render
  * record, tile rect and count; plus the caller's radii) and skips the rows kept for the backward
  * (cov3D, means2D, conic, inverse depth, radii in the workspace): 56 of 108 bytes per visible
- * Gaussian.  The batched compositing kernel (two frames or more, without the refiner epilogue)
- * then runs its forward-only instantiation, which neither tracks a pixel's last contributor nor
- * stores final_T and n_contrib: 132 instead of 140 bytes per pixel.  After such a call the image
+ * Gaussian.  The batched compositing kernel (two frames or more; with or without the refiner
+ * epilogue of gsr_forward_batch_refine) then runs its forward-only instantiation, which neither
+ * tracks a pixel's last contributor nor stores final_T and n_contrib: 132 instead of 140 bytes per
+ * pixel without the head.  A single frame (B = 1) composites on the quad-wave kernel, which has no
+ * forward-only form and stores both rows (gsr_render_variant below tells which kernel a call
+ * takes).  After such a call the image
  * arena's final_T and n_contrib rows are UNSPECIFIED (whatever an earlier call left there); the
  * next forward without the flag rewrites every pixel of both.  Images are unchanged.  A
  * gsr_backward_batch* on a workspace whose last forward was
  * forward-only fails with GSR_ERR_ARG (the library records it per workspace pointer on the host;
  * the kernels also skip such a workspace, so nothing is computed either way). */
 #define GSR_FORWARD_ONLY 0x100u
+
+/* Which compositing kernel a batched forward of B frames with this flag word (numerics bits and
+ * GSR_FORWARD_ONLY) takes, with (has_refine != 0) or without the refiner epilogue: the launcher's own
+ * selection function, so the answer cannot drift from what runs.  Host-side only: it reads no
+ * device state and launches nothing.  It answers for features shared by the batch (colors_stride 0)
+ * where that matters: per-frame features under GSR_NUMERICS_SPLIT_BF16 take
+ * GSR_RENDER_SPLIT_FRAME, which has no forward-only form.  While gsr_render_counters /
+ * gsr_render_timeline are armed it reports their instrumented kernels.  Unknown flag bits or
+ * B < 1: -GSR_ERR_ARG.
+ *   STRIP / STRIP_FWD            one wave per 64-pixel strip (two frames or more) / forward-only
+ *   SPLIT_FRAME, SPLIT_SHARED(_FWD)  the split-bf16 strip kernels
+ *   REFINE / REFINE_FWD          the strip kernel with the refiner epilogue / forward-only.  The head
+ *                                always accumulates with f32 MFMAs: GSR_NUMERICS_SPLIT_BF16 does not
+ *                                change a refine forward's colours
+ *   QUAD / QUAD_REFINE           one frame, a wave per 4x4 quad / with the refiner epilogue
+ *   HALF / HALF_SPLIT            one frame, a wave per half strip (split-bf16 single frames) */
+enum {
+    GSR_RENDER_STRIP = 0,
+    GSR_RENDER_STRIP_FWD = 1,
+    GSR_RENDER_SPLIT_FRAME = 2,
+    GSR_RENDER_SPLIT_SHARED = 3,
+    GSR_RENDER_SPLIT_SHARED_FWD = 4,
+    GSR_RENDER_REFINE = 5,
+    GSR_RENDER_REFINE_FWD = 6,
+    GSR_RENDER_QUAD = 7,
+    GSR_RENDER_QUAD_REFINE = 8,
+    GSR_RENDER_HALF = 9,
+    GSR_RENDER_HALF_SPLIT = 10,
+    GSR_RENDER_STATS = 11,         /* gsr_render_counters armed */
+    GSR_RENDER_TIMELINE = 12,      /* gsr_render_timeline armed: strip kernel */
+    GSR_RENDER_QUAD_TIMELINE = 13  /* gsr_render_timeline armed: quad kernel */
+};
+int gsr_render_variant(int B, uint32_t numerics, int has_refine);
 
 /* Scratch sizes used by gsr_forward (the three resizer requests).  Unlike the reference's
  * GeometryState, the geometry arena also holds the per-frame depth sort and the (depth chunk x tile)
@@ -238,7 +274,11 @@ int gsr_backward_batch_shared(int B, int P, int width, int height, const float* 
  *   out_refine[b][o]  = leaky_relu(channel keep+o + bias[o], negative_slope),  o < n_out
  * so the 33-channel feature image is never written nor re-read.  keep_channels + n_out <= 32.
  * Inference (main/test.py, render_motion.py) adds GSR_FORWARD_ONLY; without it the forward keeps
- * final_T and n_contrib and is differentiable through gsr_refine_backward_* below. */
+ * final_T and n_contrib and is differentiable through gsr_refine_backward_* below.  Every form
+ * writes the same bits: the forward-only kernel (B >= 2), the single-frame quad-wave kernel (B = 1)
+ * and the fused deform entry (gsr_forward_batch_deformed_refine, gsr_deform.h).
+ * GSR_NUMERICS_SPLIT_BF16 has no effect on the colours of a refine forward: the pre-contracted rows
+ * are always accumulated with f32 MFMAs. */
 typedef struct {
     const float* weight;   /* [n_out][32] (Conv2d weight [n_out,32,1,1]); used by gsr_refine_prepare */
     const float* bias;     /* [n_out] or NULL */

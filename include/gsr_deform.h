@@ -41,6 +41,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gsr.h" /* gsr_refine_epilogue (gsr_forward_batch_deformed_refine) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -168,6 +170,21 @@ int gsr_forward_batch_deformed(int B, int width, int height, const GsrDeformInpu
                                const float* tanfov, const float* backgrounds, int64_t bg_stride,
                                char* workspace, int64_t R_capacity, float* out_color, float* out_invdepth,
                                int* radii, int antialiasing, uint32_t numerics, void* stream);
+/* The same forward with the refiner-head epilogue of gsr_forward_batch_refine (include/gsr.h):
+ * colors and backgrounds are the gsr_refine_prepare'd rows, out_refine [B][n_out][H][W] gets the head's
+ * output and only out_color's channels [0, keep_channels) are written.  Same images as
+ * gsr_deform_gaussians + gsr_forward_batch_refine; forward-only like the entry above, so B >= 2
+ * composites on the forward-only refine kernel and B = 1 on the quad-wave one
+ * (gsr_render_variant(B, numerics | GSR_FORWARD_ONLY, 1)).  refine is checked as
+ * gsr_forward_batch_refine checks it (out_refine, n_out >= 1, keep_channels + n_out <= 32:
+ * GSR_ERR_ARG); NULL is gsr_forward_batch_deformed. */
+int gsr_forward_batch_deformed_refine(int B, int width, int height, const GsrDeformInputs* dg, const float* colors,
+                                      int64_t colors_stride, const float* opacities, int64_t opac_stride,
+                                      float scale_modifier, const float* viewmatrices, const float* projmatrices,
+                                      const float* tanfov, const float* backgrounds, int64_t bg_stride,
+                                      char* workspace, int64_t R_capacity, float* out_color, float* out_invdepth,
+                                      int* radii, int antialiasing, const gsr_refine_epilogue* refine,
+                                      uint32_t numerics, void* stream);
 
 /* One segment of gsr_pack_rows: for every frame b, dst[b * dst_stride + c] = src[b * src_stride + c]
  * for c in [0, width) (src == NULL writes zeros; src_stride 0 broadcasts one row to every frame). */
