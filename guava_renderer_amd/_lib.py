@@ -30,7 +30,10 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_fused_ssim", "gsr_fused_ssim_backward", "gsr_image_loss_partials", "gsr_image_loss",
            # include/gsr_loss.h
            "gsr_guava_loss_workspace_bytes", "gsr_guava_loss_partials", "gsr_guava_loss_forward",
-           "gsr_guava_loss_backward", "gsr_uv_regularizers_partials", "gsr_uv_regularizers")
+           "gsr_guava_loss_backward", "gsr_uv_regularizers_partials", "gsr_uv_regularizers",
+           # include/gsr_mesh.h
+           "gsr_mesh_raster_workspace_bytes", "gsr_mesh_raster", "gsr_mesh_visible_texels",
+           "gsr_mesh_raster_stats")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -310,6 +313,14 @@ def load(path=None):
     L.gsr_uv_regularizers_partials.restype = _i
     L.gsr_uv_regularizers.argtypes = [_i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp]
     L.gsr_uv_regularizers.restype = _i
+    L.gsr_mesh_raster_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
+    L.gsr_mesh_raster_workspace_bytes.restype = _sz
+    L.gsr_mesh_raster.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.gsr_mesh_raster.restype = _i
+    L.gsr_mesh_visible_texels.argtypes = [_i, _i, _i, _vp, _vp, _vp, _vp]
+    L.gsr_mesh_visible_texels.restype = _i
+    L.gsr_mesh_raster_stats.argtypes = [_vp, ctypes.POINTER(_i64)]
+    L.gsr_mesh_raster_stats.restype = _i
     _lib = L
     return L
 
