@@ -33,7 +33,10 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_guava_loss_backward", "gsr_uv_regularizers_partials", "gsr_uv_regularizers",
            # include/gsr_mesh.h
            "gsr_mesh_raster_workspace_bytes", "gsr_mesh_raster", "gsr_mesh_visible_texels",
-           "gsr_mesh_raster_stats")
+           "gsr_mesh_raster_stats",
+           # include/gsr_lift.h
+           "gsr_lift_vertices", "gsr_lift_uv", "gsr_lift_backward_workspace_bytes",
+           "gsr_lift_vertices_backward", "gsr_lift_uv_backward")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -321,6 +324,16 @@ def load(path=None):
     L.gsr_mesh_visible_texels.restype = _i
     L.gsr_mesh_raster_stats.argtypes = [_vp, ctypes.POINTER(_i64)]
     L.gsr_mesh_raster_stats.restype = _i
+    L.gsr_lift_vertices.argtypes = [_i] * 5 + [_vp] * 8
+    L.gsr_lift_vertices.restype = _i
+    L.gsr_lift_uv.argtypes = [_i] * 7 + [_vp] * 11
+    L.gsr_lift_uv.restype = _i
+    L.gsr_lift_backward_workspace_bytes.argtypes = [_i, _i, _i, _i]
+    L.gsr_lift_backward_workspace_bytes.restype = _sz
+    L.gsr_lift_vertices_backward.argtypes = [_i] * 5 + [_vp] * 8
+    L.gsr_lift_vertices_backward.restype = _i
+    L.gsr_lift_uv_backward.argtypes = [_i] * 7 + [_vp] * 12
+    L.gsr_lift_uv_backward.restype = _i
     _lib = L
     return L
 
