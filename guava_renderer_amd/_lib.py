@@ -36,7 +36,10 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_mesh_raster_stats",
            # include/gsr_lift.h
            "gsr_lift_vertices", "gsr_lift_uv", "gsr_lift_backward_workspace_bytes",
-           "gsr_lift_vertices_backward", "gsr_lift_uv_backward")
+           "gsr_lift_vertices_backward", "gsr_lift_uv_backward",
+           # include/gsr_extract.h
+           "gsr_extract_tiles", "gsr_extract_prepare", "gsr_extract_prepare_pruned", "gsr_extract_forward",
+           "gsr_extract_forward_pruned", "gsr_extract_backward")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -144,6 +147,17 @@ class EhmOutputs(ctypes.Structure):
 EHM_SLOTS = ("flame.shape_params", "flame.expression_params", "flame.jaw_params", "flame.eye_pose_params",
              "flame.eyelid_params", "body.shape", "body.exp", "body.global_pose", "body.body_pose",
              "body.left_hand_pose", "body.right_hand_pose", "body.head_scale", "body.joints_offset")
+
+
+class ExtractSet(ctypes.Structure):
+    """GsrExtractSet (include/gsr_extract.h): five device pointers."""
+    _fields_ = [("colors", _vp), ("opacities", _vp), ("scales", _vp), ("rotations", _vp), ("local_pos", _vp)]
+
+
+# gsr_extract layouts and flags (include/gsr_extract.h), by value
+EXTRACT_PLANAR_RAW = 0
+EXTRACT_ROWS_ACTIVATED = 1
+EXTRACT_RGB_SIGMOID = 1
 
 
 class GsrError(RuntimeError):
@@ -334,6 +348,19 @@ def load(path=None):
     L.gsr_lift_vertices_backward.restype = _i
     L.gsr_lift_uv_backward.argtypes = [_i] * 7 + [_vp] * 12
     L.gsr_lift_uv_backward.restype = _i
+    _xs = ctypes.POINTER(ExtractSet)
+    L.gsr_extract_tiles.argtypes = [_i]
+    L.gsr_extract_tiles.restype = _i
+    L.gsr_extract_prepare.argtypes = [_i, _vp, _vp, _vp]
+    L.gsr_extract_prepare.restype = _i
+    L.gsr_extract_prepare_pruned.argtypes = [_i, _i, _vp, _vp, _f, _vp, _vp]
+    L.gsr_extract_prepare_pruned.restype = _i
+    L.gsr_extract_forward.argtypes = [_i, _i, _i, _i, _i, _u32, _vp, _vp, _xs, _xs, _vp, _vp, _vp, _vp, _vp]
+    L.gsr_extract_forward.restype = _i
+    L.gsr_extract_forward_pruned.argtypes = [_i, _i, _i, _i, _u32, _f, _vp, _vp, _vp, _xs, _xs, _vp, _vp, _vp, _vp, _vp]
+    L.gsr_extract_forward_pruned.restype = _i
+    L.gsr_extract_backward.argtypes = [_i, _i, _i, _i, _i, _u32, _vp, _vp, _xs, _xs, _xs, _vp]
+    L.gsr_extract_backward.restype = _i
     _lib = L
     return L
 
