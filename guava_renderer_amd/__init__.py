@@ -2,7 +2,7 @@
 load the library on first use; the names below are resolved lazily so that importing the package
 stays free of both."""
 
-_LAZY = {"UVGaussianExtractor": "gaussian_extract"}
+_LAZY = {"UVGaussianExtractor": "gaussian_extract", "StyleDecoder": "refiner", "StyleUNetRunner": "refiner"}
 
 __all__ = sorted(_LAZY)
 

@@ -39,7 +39,9 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_lift_vertices_backward", "gsr_lift_uv_backward",
            # include/gsr_extract.h
            "gsr_extract_tiles", "gsr_extract_prepare", "gsr_extract_prepare_pruned", "gsr_extract_forward",
-           "gsr_extract_forward_pruned", "gsr_extract_backward")
+           "gsr_extract_forward_pruned", "gsr_extract_backward",
+           # include/gsr_refiner.h
+           "gsr_style_coeffs", "gsr_style_upmod", "gsr_style_epilogue", "gsr_style_torgb")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -158,6 +160,12 @@ class ExtractSet(ctypes.Structure):
 EXTRACT_PLANAR_RAW = 0
 EXTRACT_ROWS_ACTIVATED = 1
 EXTRACT_RGB_SIGMOID = 1
+
+
+class StyleLayer(ctypes.Structure):
+    """GsrStyleLayer (include/gsr_refiner.h): one modulated conv of a decoder."""
+    _fields_ = [("s_off", ctypes.c_int32), ("c_in", ctypes.c_int32), ("d_off", ctypes.c_int32),
+                ("c_out", ctypes.c_int32), ("w2_off", ctypes.c_int32), ("eps", _f)]
 
 
 class GsrError(RuntimeError):
@@ -361,6 +369,14 @@ def load(path=None):
     L.gsr_extract_forward_pruned.restype = _i
     L.gsr_extract_backward.argtypes = [_i, _i, _i, _i, _i, _u32, _vp, _vp, _xs, _xs, _xs, _vp]
     L.gsr_extract_backward.restype = _i
+    L.gsr_style_coeffs.argtypes = [_i, _i, _i, ctypes.POINTER(StyleLayer), _i, _i, _i64] + [_vp] * 7
+    L.gsr_style_coeffs.restype = _i
+    L.gsr_style_upmod.argtypes = [_i] * 6 + [_vp, _vp, _i64, _vp, _vp]
+    L.gsr_style_upmod.restype = _i
+    L.gsr_style_epilogue.argtypes = [_i, _i, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]
+    L.gsr_style_epilogue.restype = _i
+    L.gsr_style_torgb.argtypes = [_i] * 5 + [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp]
+    L.gsr_style_torgb.restype = _i
     _lib = L
     return L
 
