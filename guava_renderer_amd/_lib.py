@@ -41,7 +41,9 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geometry_bytes",
            "gsr_extract_tiles", "gsr_extract_prepare", "gsr_extract_prepare_pruned", "gsr_extract_forward",
            "gsr_extract_forward_pruned", "gsr_extract_backward",
            # include/gsr_refiner.h
-           "gsr_style_coeffs", "gsr_style_upmod", "gsr_style_epilogue", "gsr_style_torgb")
+           "gsr_style_coeffs", "gsr_style_upmod", "gsr_style_epilogue", "gsr_style_torgb",
+           "gsr_style_backward_chunks", "gsr_style_epilogue_backward", "gsr_style_upmod_backward",
+           "gsr_style_torgb_backward", "gsr_style_coeffs_backward")
 
 # per-call numerics flags (include/gsr.h GSR_NUMERICS_*); 0 = bit-identical to the CPU oracle
 NUMERICS_EXACT = 0
@@ -377,6 +379,17 @@ def load(path=None):
     L.gsr_style_epilogue.restype = _i
     L.gsr_style_torgb.argtypes = [_i] * 5 + [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp]
     L.gsr_style_torgb.restype = _i
+    L.gsr_style_backward_chunks.argtypes = [_i, _i]
+    L.gsr_style_backward_chunks.restype = _i64
+    L.gsr_style_epilogue_backward.argtypes = ([_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64]
+                                              + [_vp] * 9)
+    L.gsr_style_epilogue_backward.restype = _i
+    L.gsr_style_upmod_backward.argtypes = [_i] * 6 + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]
+    L.gsr_style_upmod_backward.restype = _i
+    L.gsr_style_torgb_backward.argtypes = [_i] * 5 + [_vp, _vp, _vp, _vp, _vp, _i64, _i] + [_vp] * 7
+    L.gsr_style_torgb_backward.restype = _i
+    L.gsr_style_coeffs_backward.argtypes = [_i, _i, ctypes.POINTER(StyleLayer), _i, _i, _i64] + [_vp] * 7
+    L.gsr_style_coeffs_backward.restype = _i
     _lib = L
     return L
 

@@ -18,7 +18,7 @@ OBJ_DIR = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(LIB_DIR, "libgsr.so")
 SOURCES = ["preprocess.hip", "binning.hip", "render_fwd.hip", "render_bwd.hip",
            "preprocess_bwd.hip", "refine_bwd.hip", "deform.hip", "ehm.hip", "ssim.hip", "loss.hip", "frames.hip", "mesh_raster.hip",
-           "lift.hip", "extract.hip", "refiner.hip", "capi.hip"]
+           "lift.hip", "extract.hip", "refiner.hip", "refiner_bwd.hip", "capi.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",

@@ -110,4 +110,108 @@ GSR_RF_HD void rf_torgb(const float* wm, const float* bias, const float* x, int6
         for (int k = 0; k < 4; ++k) acc[o].v[k] = acc[o].v[k] + bias[o];
 }
 
+// ------------------------------------------------------------------ backward (refiner_bwd.hip)
+
+constexpr int kRfChunkQuads = 256;  // lane-quads of one reduction chunk: one workgroup, a quad per lane
+constexpr int kRfW2Slabs = 8;       // workgroups per layer that share the g_w2 table of gsr_style_coeffs_backward
+
+// chunks of a plane of H x W (W a multiple of 4): a function of the shape alone
+GSR_RF_HD int64_t rf_chunks(int64_t plane_quads) { return (plane_quads + kRfChunkQuads - 1) / kRfChunkQuads; }
+
+// An index one step outside an axis of n output samples is folded back onto the border sample: it is the
+// border sample's clamped farther tap (rf_up_index) that lands there.
+GSR_RF_HD int rf_fold(int r, int n) { return r < 0 ? 0 : (r > n - 1 ? n - 1 : r); }
+
+// The transposed tap pair along one axis: an input sample collects the four output samples 2i - 1 .. 2i + 2
+// with rf_tap's weights, in ascending index order.
+GSR_RF_HD float rf_tap_t(float a, float b, float c, float d) {
+    return ((0.25f * a + 0.75f * b) + 0.75f * c) + 0.25f * d;
+}
+
+// up2T(g)[i][c]: the transpose of up2.  g is the 2h x 2w plane (H = 2h, W = 2w), read through at(r, j).
+// Columns first, then rows (up2 runs rows first, so this is its exact reverse):
+//   u(k) = rf_tap_t(g[r_k][fold(2c-1)], g[r_k][2c], g[r_k][2c+1], g[r_k][fold(2c+2)]),  r_k = fold(2i-1+k)
+//   up2T = rf_tap_t(u(0), u(1), u(2), u(3)).
+template <class At>
+GSR_RF_HD float rf_up2t(const At& at, int H, int W, int i, int c) {
+    const int j0 = rf_fold(2 * c - 1, W), j3 = rf_fold(2 * c + 2, W);
+    float u[4];
+    for (int k = 0; k < 4; ++k) {
+        const int r = rf_fold(2 * i - 1 + k, H);
+        u[k] = rf_tap_t(at(r, j0), at(r, 2 * c), at(r, 2 * c + 1), at(r, j3));
+    }
+    return rf_tap_t(u[0], u[1], u[2], u[3]);
+}
+
+// g read from a plane as it is
+struct RfAtPlain {
+    const float* g;
+    int W;
+    GSR_RF_HD float operator()(int r, int j) const { return g[(int64_t)r * W + j]; }
+};
+
+// the gradient through the sigmoid, from the saved output y
+GSR_RF_HD float rf_sigmoid_bwd(float g, float y) { return g * (y * (1.0f - y)); }
+
+// g_acc of a ToRGB read in place: g_out, or g_out through the sigmoid of the saved output y (y != nullptr)
+struct RfAtAcc {
+    const float* g;
+    const float* y;
+    int W;
+    GSR_RF_HD float operator()(int r, int j) const {
+        const int64_t e = (int64_t)r * W + j;
+        return y ? rf_sigmoid_bwd(g[e], y[e]) : g[e];
+    }
+};
+
+// a lane's share of a reduction over pixels: the four products of its quad, summed pairwise
+GSR_RF_HD float rf_quad_sum(const RfQuad& t) { return (t.v[0] + t.v[1]) + (t.v[2] + t.v[3]); }
+GSR_RF_HD float rf_quad_dot(const RfQuad& a, const RfQuad& b) {
+    return (a.v[0] * b.v[0] + a.v[1] * b.v[1]) + (a.v[2] * b.v[2] + a.v[3] * b.v[3]);
+}
+
+// The StyleConv epilogue's backward of one element.  v and l are recomputed with the forward's
+// expressions and the forward's branch (v >= 0: slope 1; otherwise, a NaN included, 0.2f):
+//   g1 = g_y * post (g_y without a post);  y1 = l*scale + shift (l without the SFT maps)
+//   gl = g1 * scale (g1 without);  g_v = v >= 0 ? gl : 0.2f * gl
+//   g_x = a * g_v;  g_scale = g1 * l;  g_shift = g1
+// and the element's terms of the plane sums: g_v * x, g_v, g_y * y1 in float32.  The noise weight's
+// gradient reduces the whole tensor to one number, the most cancellation-prone sum of all: its terms
+// g_v * noise are formed and added in float64 (rf_noise_term: exact products).
+struct RfEpiGrad {
+    float g_x, g_scale, g_shift;
+    float t_x, g_v, t_post;
+};
+GSR_RF_HD double rf_noise_term(float g_v, float noise) { return (double)g_v * (double)noise; }
+GSR_RF_HD RfEpiGrad rf_epilogue_bwd(float gy, float x, float a, float nw, float noise, float bias, bool sft, float scale,
+                                    float shift, bool has_post, float post) {
+    const float v = ((a * x) + (nw * noise)) + bias;
+    const bool pos = v >= 0.0f;
+    const float l = pos ? v : kRfSlope * v;
+    const float g1 = has_post ? gy * post : gy;
+    const float y1 = sft ? rf_sft(l, scale, shift) : l;
+    const float gl = sft ? g1 * scale : g1;
+    RfEpiGrad r;
+    r.g_v = pos ? gl : kRfSlope * gl;
+    r.g_x = a * r.g_v;
+    r.g_scale = g1 * l;
+    r.g_shift = g1;
+    r.t_x = r.g_v * x;
+    r.t_post = gy * y1;
+    return r;
+}
+
+// ToRGB backward, channel c of four pixels: g_x = wm[c]*g[0]; g_x = g_x + wm[o*C + c]*g[o], o ascending.
+template <int O>
+GSR_RF_HD RfQuad rf_torgb_bwd_x(const float* wm, int C, int c, const RfQuad g[O]) {
+    RfQuad r;
+    for (int k = 0; k < 4; ++k) r.v[k] = wm[c] * g[0].v[k];
+    for (int o = 1; o < O; ++o)
+        for (int k = 0; k < 4; ++k) r.v[k] = r.v[k] + wm[o * C + c] * g[o].v[k];
+    return r;
+}
+
+// Demodulation backward: t = -0.5 * d^3 * g_d, d as the forward stored it.
+GSR_RF_HD float rf_demod_bwd(float d, float g_d) { return (-0.5f * ((d * d) * d)) * g_d; }
+
 }  // namespace gsr

@@ -6,20 +6,28 @@ it is one HIP pass in front (upsample + input modulation) and one behind (demodu
 LeakyReLU, SFT), plus one launch for every layer's s and d and one fused ToRGB per level.
 
   StyleDecoder.from_module(dec) / .from_state_dict(sd, out_size, small)
-      .forward(style_code [B,S], conditions, noise=None, generator=None, sigmoid=False) -> [B,out_dim,H,W]
+      .forward(style_code [B,S], conditions, noise=None, generator=None, sigmoid=False, grad=False)
+                                                                                   -> [B,out_dim,H,W]
   StyleUNetRunner(styleunet)
       .forward(x32, ...)    the whole refiner on the 32-channel render
       .rest(feat16, ...)    from RefineHead.out / render_refined's `refined` (conv_body_first + LeakyReLU)
 
-Forward only, float32, on the caller's current stream.  Semantics: include/gsr_refiner.h (DESIGN.md
-5.9).  GPU only: CPU tensors raise RuntimeError; there is no CPU fallback.  With grad enabled and an
-input or parameter that requires it, NotImplementedError: there is no backward yet.
+Float32, on the caller's current stream.  Semantics: include/gsr_refiner.h.  GPU only:
+CPU tensors raise RuntimeError; there is no CPU fallback.
+
+The default calls are forward only: with grad enabled and an input or parameter that requires it they
+raise NotImplementedError.  Training is opt-in: grad=True runs the same forward kernels (bit-equal
+values, the epilogue out of place) under torch.autograd, with the backward of the four kernels in HIP
+(csrc/refiner_bwd.hip: style_upmod_grad, style_epilogue_grad, style_torgb_grad, style_coeffs_grad) and
+the convolutions, the style MLP, normal_convs and the UNet half under ordinary autograd.  Noise tensors
+get no gradient; there is no double backward.
 """
 import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -156,6 +164,234 @@ def style_torgb(x, weight, s, bias, skip=None, skip_up=False, sigmoid=False):
     return out
 
 
+# ------------------------------------------------------------------ their backward (csrc/refiner_bwd.hip)
+
+def _chunks(H, W):
+    n = int(_lib.load().gsr_style_backward_chunks(int(H), int(W)))
+    return max(n, 1)  # (a refused shape: the entry itself reports it, with nothing launched)
+
+
+def _layer_table(layers):
+    return (_lib.StyleLayer * len(layers))(*[_lib.StyleLayer(int(a), int(b), int(c), int(d), int(e), float(f))
+                                             for a, b, c, d, e, f in layers])
+
+
+def _f32(shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def style_upmod_backward(g_y, x, s, up=True):
+    """gsr_style_upmod_backward -> (g_x shaped as x, g_s [B,C])."""
+    g_y, x = _gpu(g_y, "g_y", 4), _gpu(x, "x", 4).contiguous()
+    if not g_y.is_contiguous():
+        raise RuntimeError("g_y must be contiguous")
+    B, C, H, W = g_y.shape
+    s, ss = _rows(s, "s", B, C)
+    xb = int(x.shape[0])
+    want = (xb, C, H // 2, W // 2) if up else (xb, C, H, W)
+    if xb not in (1, B) or tuple(x.shape) != want or (up and (H % 2 or W % 2)):
+        raise RuntimeError(f"x must be (1 or {B}, {C}, {want[2]}, {want[3]}), got {tuple(x.shape)}")
+    dev = g_y.device
+    g_x, g_s = torch.empty_like(x), _f32((B, C), dev)
+    ws = _f32((B * C * _chunks(H, W),), dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsr_style_upmod_backward(B, C, H, W, 1 if up else 0, xb, _p(g_y), _p(x), _p(s), ss, _p(g_x),
+                                                        _p(g_s), _p(ws), _stream(dev)), "gsr_style_upmod_backward")
+    return g_x, g_s
+
+
+def style_epilogue_backward(g_y, x, d, bias, noise=None, noise_weight=None, scale=None, shift=None, post=None):
+    """gsr_style_epilogue_backward on the forward's operands (x: what the forward read)
+    -> dict(x, d, bias [C], noise_weight [1], scale, shift, post), None where the operand is absent."""
+    g_y, x = _gpu(g_y, "g_y", 4), _gpu(x, "x", 4)
+    if not x.is_contiguous() or not g_y.is_contiguous():
+        raise RuntimeError("x and g_y must be contiguous")
+    if tuple(g_y.shape) != tuple(x.shape):
+        raise RuntimeError(f"g_y must be {tuple(x.shape)}, got {tuple(g_y.shape)}")
+    B, C, H, W = x.shape
+    d, ds = _rows(d, "d", B, C) if d is not None else (None, 0)
+    post, ps = _rows(post, "post", B, C) if post is not None else (None, 0)
+    bias = _gpu(bias, "bias").reshape(-1).contiguous()
+    if bias.numel() != C:
+        raise RuntimeError(f"bias must hold {C} values, got {tuple(bias.shape)}")
+    nb = 0
+    if noise is not None:
+        noise = _gpu(noise, "noise", 4).contiguous()
+        nb = int(noise.shape[0])
+        if tuple(noise.shape[1:]) != (1, H, W) or nb not in (1, B):
+            raise RuntimeError(f"noise must be (1 or {B}, 1, {H}, {W}), got {tuple(noise.shape)}")
+        noise_weight = _gpu(noise_weight, "noise_weight").reshape(-1)
+    if (scale is None) != (shift is None):
+        raise RuntimeError("scale and shift come together")
+    if scale is not None:
+        scale, shift = _gpu(scale, "scale", 4).contiguous(), _gpu(shift, "shift", 4).contiguous()
+        if tuple(scale.shape) != tuple(x.shape) or tuple(shift.shape) != tuple(x.shape):
+            raise RuntimeError(f"scale and shift must be {tuple(x.shape)}, got {tuple(scale.shape)} and "
+                               f"{tuple(shift.shape)}")
+    dev = x.device
+    g = dict(x=torch.empty_like(x), bias=_f32((C,), dev),
+             d=_f32((B, C), dev) if d is not None else None, post=_f32((B, C), dev) if post is not None else None,
+             noise_weight=_f32((1,), dev) if nb else None,
+             scale=torch.empty_like(x) if scale is not None else None,
+             shift=torch.empty_like(x) if scale is not None else None)
+    ws = _f32((6 * B * C * (_chunks(H, W) + 1),), dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsr_style_epilogue_backward(
+            B, C, H, W, _p(g_y), _p(x), _p(d), ds, _p(noise), nb, _p(noise_weight) if nb else None, _p(bias), _p(scale),
+            _p(shift), _p(post), ps, _p(g["x"]), _p(g["scale"]), _p(g["shift"]), _p(g["d"]), _p(g["post"]), _p(g["bias"]),
+            _p(g["noise_weight"]), _p(ws), _stream(dev)), "gsr_style_epilogue_backward")
+    return g
+
+
+def style_torgb_backward(g_out, x, weight, s, y=None, skip=None):
+    """gsr_style_torgb_backward.  y: the forward's output where it applied the sigmoid, else None; skip:
+    None, "same" or "up" (how the forward took its skip) -> (g_x, g_weight [O,C], g_s [B,C], g_bias [O],
+    g_skip or None)."""
+    g_out, x = _gpu(g_out, "g_out", 4), _gpu(x, "x", 4).contiguous()
+    if not g_out.is_contiguous():
+        raise RuntimeError("g_out must be contiguous")
+    B, C, H, W = x.shape
+    weight = _gpu(weight, "weight", 2).contiguous()
+    O = int(weight.shape[0])
+    if weight.shape[1] != C or tuple(g_out.shape) != (B, O, H, W):
+        raise RuntimeError(f"weight must be (out_dim, {C}) and g_out ({B}, out_dim, {H}, {W}), got {tuple(weight.shape)} "
+                           f"and {tuple(g_out.shape)}")
+    s, ss = _rows(s, "s", B, C)
+    if y is not None:
+        y = _gpu(y, "y", 4).contiguous()
+        if tuple(y.shape) != tuple(g_out.shape):
+            raise RuntimeError(f"y must be {tuple(g_out.shape)}, got {tuple(y.shape)}")
+    if skip not in (None, "same", "up") or (skip == "up" and (H % 2 or W % 2)):
+        raise RuntimeError(f"skip must be None, 'same' or 'up' (even sizes), got {skip!r}")
+    dev = x.device
+    g_x, g_w, g_s, g_b = torch.empty_like(x), _f32((O, C), dev), _f32((B, C), dev), _f32((O,), dev)
+    g_skip = None if skip is None else _f32((B, O, H // 2, W // 2) if skip == "up" else (B, O, H, W), dev)
+    ws = _f32((B * _chunks(H, W) * (O * C + O),), dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gsr_style_torgb_backward(B, C, O, H, W, _p(g_out), _p(y), _p(x), _p(weight), _p(s), ss,
+                                                        1 if skip == "up" else 0, _p(g_x), _p(g_skip), _p(g_w), _p(g_s),
+                                                        _p(g_b), _p(ws), _stream(dev)), "gsr_style_torgb_backward")
+    return g_x, g_w, g_s, g_b, g_skip
+
+
+def style_coeffs_backward(g_s, g_d, s, d, w2, layers):
+    """gsr_style_coeffs_backward: the demodulation's share.  g_s [B,sum_in] (what reached s directly; not
+    modified), g_d [B,sum_out] -> (g_s with the demodulated layers' share added, g_w2 shaped as w2)."""
+    g_s, s = _gpu(g_s, "g_s", 2), _gpu(s, "s", 2).contiguous()
+    B, sum_in = s.shape
+    if tuple(g_s.shape) != (B, sum_in):
+        raise RuntimeError(f"g_s must be {(B, sum_in)}, got {tuple(g_s.shape)}")
+    g_s = g_s.clone(memory_format=torch.contiguous_format)
+    if d is None:
+        return g_s, None
+    d, g_d, w2 = _gpu(d, "d", 2).contiguous(), _gpu(g_d, "g_d", 2).contiguous(), _gpu(w2, "w2", 1).contiguous()
+    if tuple(g_d.shape) != tuple(d.shape) or d.shape[0] != B:
+        raise RuntimeError(f"d and g_d must be ({B}, sum_out), got {tuple(d.shape)} and {tuple(g_d.shape)}")
+    covered = sum(int(c_in) * int(c_out) for _, c_in, d_off, c_out, _, _ in layers if d_off >= 0)
+    g_w2 = torch.empty_like(w2) if covered == w2.numel() else torch.zeros_like(w2)
+    with torch.cuda.device(s.device):
+        _lib.check(_lib.load().gsr_style_coeffs_backward(B, len(layers), _layer_table(layers), sum_in, int(d.shape[1]),
+                                                         w2.numel(), _p(s), _p(d), _p(w2), _p(g_d), _p(g_s), _p(g_w2),
+                                                         _stream(s.device)), "gsr_style_coeffs_backward")
+    return g_s, g_w2
+
+
+def _like(g, t):
+    """A gradient in the shape of the operand it belongs to (None stays None)."""
+    return None if g is None or t is None else g.reshape(t.shape)
+
+
+class _Upmod(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, s, up):
+        ctx.save_for_backward(x, s)
+        ctx.up = up
+        return style_upmod(x, s, up=up)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        x, s = ctx.saved_tensors
+        g_x, g_s = style_upmod_backward(g_y.contiguous(), x, s, up=ctx.up)
+        return _like(g_x, x), g_s, None
+
+
+class _Epilogue(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, d, bias, noise, noise_weight, scale, shift, post):
+        ctx.save_for_backward(x, d, bias, noise, noise_weight, scale, shift, post)
+        return style_epilogue(x, d, bias, noise, noise_weight, scale, shift, post)  # out of place: x is kept
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        x, d, bias, noise, nw, scale, shift, post = ctx.saved_tensors
+        g = style_epilogue_backward(g_y.contiguous(), x, d, bias, noise, nw, scale, shift, post)
+        return (g["x"], g["d"], _like(g["bias"], bias), None, _like(g["noise_weight"], nw), _like(g["scale"], scale),
+                _like(g["shift"], shift), g["post"])
+
+
+class _ToRGB(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, s, bias, skip, skip_up, sigmoid):
+        out = style_torgb(x, weight, s, bias, skip, skip_up=skip_up, sigmoid=sigmoid)
+        ctx.save_for_backward(x, weight, s, bias, out if sigmoid else None)
+        ctx.skip = None if skip is None else ("up" if skip_up else "same")
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, weight, s, bias, y = ctx.saved_tensors
+        g_x, g_w, g_s, g_b, g_skip = style_torgb_backward(g_out.contiguous(), x, weight, s, y=y, skip=ctx.skip)
+        return _like(g_x, x), _like(g_w, weight), g_s, _like(g_b, bias), g_skip, None, None
+
+
+class _Coeffs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, latent, mod_weight, mod_bias, w2, layers, sum_out):
+        s, d = style_coeffs(latent, mod_weight, mod_bias, w2, layers, sum_out)
+        if d is None:  # no demodulated layer: an empty table stands in, without a gradient
+            d = latent.new_empty((latent.shape[0], 0))
+            ctx.mark_non_differentiable(d)
+        ctx.save_for_backward(latent, mod_weight, w2, s, d)
+        ctx.layers = layers
+        return s, d
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, g_d):
+        latent, mod_weight, w2, s, d = ctx.saved_tensors
+        g_s, g_w2 = style_coeffs_backward(g_s, g_d, s, d if d.shape[1] else None, w2, ctx.layers)
+        # the three dense products are rocBLAS GEMMs on the stacked tables: plumbing, and already one
+        # launch each for every layer at once
+        return torch.mm(g_s, mod_weight), torch.mm(g_s.t(), latent), g_s.sum(0), g_w2, None, None
+
+
+def style_upmod_grad(x, s, up=True):
+    """style_upmod under torch.autograd: gradients for x and s."""
+    return _Upmod.apply(_gpu(x, "x", 4), s, bool(up))
+
+
+def style_epilogue_grad(x, d, bias, noise=None, noise_weight=None, scale=None, shift=None, post=None):
+    """style_epilogue (out of place) under torch.autograd: gradients for x, d, bias, noise_weight, scale,
+    shift and post; none for the noise."""
+    return _Epilogue.apply(x, d, bias, noise, noise_weight if noise is not None else None, scale, shift, post)
+
+
+def style_torgb_grad(x, weight, s, bias, skip=None, skip_up=False, sigmoid=False):
+    """style_torgb under torch.autograd: gradients for x, weight, s, bias and skip."""
+    return _ToRGB.apply(x, weight, s, bias, skip, bool(skip_up), bool(sigmoid))
+
+
+def style_coeffs_grad(latent, mod_weight, mod_bias, w2, layers, sum_out):
+    """style_coeffs under torch.autograd: gradients for latent, mod_weight, mod_bias and w2."""
+    if w2 is None:
+        w2 = latent.new_zeros((0,))
+    s, d = _Coeffs.apply(latent, mod_weight, mod_bias, w2, tuple(tuple(l) for l in layers), int(sum_out))
+    return s, (d if sum_out else None)
+
+
 # ------------------------------------------------------------------ the decoder
 
 def _no_backward(tensors, what):
@@ -174,9 +410,10 @@ def _module_get(root):
 
 
 class StyleDecoder:
-    """StyleGAN2GeneratorCSFT / StyleGAN2GeneratorCSFT_small, forward only.  Holds references to the
-    parameters it was built from (no copies of the conv weights); the stacked modulation weights and
-    the sum-of-squares tables are copies: call invalidate() after a weight update."""
+    """StyleGAN2GeneratorCSFT / StyleGAN2GeneratorCSFT_small.  Holds references to the parameters it was
+    built from (no copies of the conv weights); the stacked modulation weights and the sum-of-squares
+    tables of the no-grad path are copies: call invalidate() after a weight update.  forward(grad=True)
+    builds those tables from the live parameters on every call and is differentiable."""
 
     def __init__(self, get, small, levels, mlp_index, eps=1e-8):
         self._get, self.small, self.levels, self._mlp_index = get, bool(small), int(levels), tuple(mlp_index)
@@ -261,7 +498,7 @@ class StyleDecoder:
             self.mod_weight = torch.cat([m["mod_w"] for m in mods]).contiguous()
             self.mod_bias = torch.cat([m["mod_b"] for m in mods]).contiguous()
             self.w2 = torch.cat(w2).contiguous()
-        self.table, self.sum_out = table, d_off
+        self.table, self.sum_out, self._mods = table, d_off, mods
         self.num_noise = 1 + self.levels * (1 if self.small else 2)
         self.out_dim = int(self.rgb1["weight"].shape[1])
         self.num_style_feat = int(self.mod_weight.shape[1])
@@ -294,14 +531,17 @@ class StyleDecoder:
         y = F.conv2d(x, m["conv_w"], padding=m["conv_w"].shape[-1] // 2)
         return style_epilogue(y, d[:, m["d"][0]:m["d"][1]], m["bias"], noise, m["nw"], scale, shift, post, out=y)
 
-    def forward(self, style_code, conditions, noise=None, generator=None, sigmoid=False):
+    def forward(self, style_code, conditions, noise=None, generator=None, sigmoid=False, grad=False):
         """style_code [B,S]; conditions: the SFT maps, scale and shift alternating, as StyleUNet.forward
         builds them; noise: None (fresh normals per style conv, from `generator`) or one tensor
-        [1 or B,1,h,w] per style conv; sigmoid: StyleUNet's final activation, fused into the last ToRGB."""
+        [1 or B,1,h,w] per style conv; sigmoid: StyleUNet's final activation, fused into the last ToRGB;
+        grad: differentiable (the same values; with grad disabled it is the plain forward)."""
         _gpu(style_code, "style_code", 2)
         conditions = [_gpu(c, "a condition map", 4) for c in conditions]
         if noise is not None:
             noise = [_gpu(n, "a noise tensor", 4) for n in noise]
+        if grad and torch.is_grad_enabled():
+            return self._forward_grad(style_code, conditions, noise, generator, sigmoid)
         _no_backward([style_code] + conditions + list(noise or ()) + self.parameters(), "StyleDecoder.forward")
         B, dev = int(style_code.shape[0]), style_code.device
         noise = self._noise(noise, generator, B, dev)
@@ -333,6 +573,56 @@ class StyleDecoder:
                                sigmoid=sigmoid and last)
         return skip
 
+    def _forward_grad(self, style_code, conditions, noise, generator, sigmoid):
+        """forward() under autograd: the same kernels on the same values, the tables built from the live
+        parameters with differentiable torch ops, the epilogue out of place (its backward reads the conv
+        output), the convs, the MLP and normal_convs under torch's own autograd."""
+        B, dev = int(style_code.shape[0]), style_code.device
+        noise = [n.detach() for n in self._noise(noise, generator, B, dev)]
+        mods = self._mods
+        demod = [m for m in mods if "nw" in m]
+        mod_weight = torch.cat([m["mod_w"] for m in mods]).contiguous()
+        mod_bias = torch.cat([m["mod_b"] for m in mods]).contiguous()
+        w2 = torch.cat([m["weight"][0].pow(2).sum((-1, -2)).reshape(-1) for m in demod]).contiguous()
+        lat = style_code * torch.rsqrt(torch.mean(style_code ** 2, dim=1, keepdim=True) + 1e-8)
+        for w, b in self.mlp:
+            lat = F.leaky_relu_(F.linear(lat, w, b), 0.2)
+        s, d = style_coeffs_grad(lat, mod_weight, mod_bias, w2, self.table, self.sum_out)
+        # one split (one cat in the backward) instead of a slice per layer
+        s_of = {id(m): t for m, t in zip(mods, s.split([m["s"][1] - m["s"][0] for m in mods], dim=1))}
+        d_of = {id(m): t for m, t in zip(demod, d.split([m["d"][1] - m["d"][0] for m in demod], dim=1))}
+
+        def style_conv(x, m, n, up, scale=None, shift=None, post=None, modulated=False):
+            if not modulated:
+                x = style_upmod_grad(x, s_of[id(m)], up=up)
+            w = m["weight"][0]
+            y = F.conv2d(x, w, padding=w.shape[-1] // 2)
+            return style_epilogue_grad(y, d_of[id(m)], m["bias"], n, m["nw"], scale, shift, post)
+
+        def to_rgb(x, m, skip, last):
+            w = m["weight"]
+            return style_torgb_grad(x, w.reshape(w.shape[1], w.shape[2]), s_of[id(m)], m["bias"], skip=skip,
+                                    skip_up=skip is not None, sigmoid=sigmoid and last)
+
+        out = style_conv(self.const, self.conv1, noise[0], up=False)
+        skip = to_rgb(out, self.rgb1, None, self.levels == 0)
+        n = 1
+        for k, lv in enumerate(self.level):
+            i = 1 + k if self.small else 1 + 2 * k  # the reference's index arithmetic, as in forward()
+            c0 = (i - 1) * 2 if self.small else i - 1
+            scale, shift = (conditions[c0], conditions[c0 + 1]) if i < len(conditions) else (None, None)
+            post = s_of[id(lv["b"])] if lv["b"] is not None else None
+            out = style_conv(out, lv["a"], noise[n], up=True, scale=scale, shift=shift, post=post)
+            n += 1
+            if self.small:
+                w, b = lv["normal"]
+                out = F.leaky_relu_(F.conv2d(out, w, b, padding=w.shape[-1] // 2), 0.2)
+            else:
+                out = style_conv(out, lv["b"], noise[n], up=False, modulated=True)
+                n += 1
+            skip = to_rgb(out, lv["rgb"], skip, k == self.levels - 1)
+        return skip
+
     __call__ = forward
 
 
@@ -348,27 +638,31 @@ class StyleUNetRunner:
     def invalidate(self):
         self.decoder.invalidate()
 
-    def _check(self, x, what, noise, extra_style):
+    def _check(self, x, what, noise, extra_style, grad=False):
         _gpu(x, what, 4)
+        if grad:
+            return
         params = [p for p in self.net.parameters()] if hasattr(self.net, "parameters") else self.decoder.parameters()
         _no_backward([x, extra_style] + list(noise or ()) + params, "StyleUNetRunner")
 
-    def forward(self, x, noise=None, generator=None, extra_style=None):
-        """x: the 32-channel render [B,in_dim,h,w] -> the refined image [B,out_dim,out_size,out_size]."""
+    def forward(self, x, noise=None, generator=None, extra_style=None, grad=False):
+        """x: the 32-channel render [B,in_dim,h,w] -> the refined image [B,out_dim,out_size,out_size].
+        grad: differentiable with respect to x and every parameter of the module (the UNet half through
+        torch's autograd, the decoder through StyleDecoder.forward(grad=True)); the same values."""
         net = self.net
-        self._check(x, "x", noise, extra_style)
+        self._check(x, "x", noise, extra_style, grad)
         if x.shape[-1] < net.out_size:
             x = F.interpolate(x, size=(net.out_size, net.out_size), mode="bilinear", align_corners=False)
         if net.in_size <= net.out_size:
             feat = F.leaky_relu_(net.conv_body_first(x), negative_slope=0.2)
         else:
             feat = net.conv_body_first[1](F.leaky_relu_(net.conv_body_first[0](x), negative_slope=0.2))
-        return self.rest(feat, noise=noise, generator=generator, extra_style=extra_style)
+        return self.rest(feat, noise=noise, generator=generator, extra_style=extra_style, grad=grad)
 
-    def rest(self, feat, noise=None, generator=None, extra_style=None):
+    def rest(self, feat, noise=None, generator=None, extra_style=None, grad=False):
         """feat: conv_body_first + LeakyReLU of the render (RefineHead.out, render_refined's `refined`)."""
         net = self.net
-        self._check(feat, "feat", noise, extra_style)
+        self._check(feat, "feat", noise, extra_style, grad)
         skips = []
         for down in net.conv_body_down:
             feat = down(feat)
@@ -381,6 +675,7 @@ class StyleUNetRunner:
         for i, up in enumerate(net.conv_body_up):
             feat = up(feat + skips[i])
             conditions += [net.condition_scale[i](feat), net.condition_shift[i](feat)]
-        return self.decoder.forward(style, conditions, noise=noise, generator=generator, sigmoid=bool(net.activation))
+        return self.decoder.forward(style, conditions, noise=noise, generator=generator, sigmoid=bool(net.activation),
+                                    grad=grad)
 
     __call__ = forward
